@@ -1,7 +1,27 @@
 """Benchmark: zfp fixed-rate encode+decode, device-resident, on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU)
+
+A plain run does only what the headline figure needs: it builds the input,
+captures the step's hipGraph, brings the GPU to the clocks it holds under load,
+runs the W warmup steps, times the K steps, writes the last step's outputs if
+--dump-outputs is given, and prints the result line (metric, value, unit,
+ms_per_step, ...).  Everything else the benchmark measures or checks -- the
+per-kernel times and roofline, the copy calibrator, the CPU baseline, the host
+path, the stream all-gather, BASELINE's other configurations and every
+comparison with the reference's digests -- runs only with --full, which
+prints the line described below.
+
+--dump-outputs DIR writes what the timed step returned to its caller, after
+the timed steps: DIR/stream.npy (the compressed stream, as its 16-bit pieces in
+little-endian order, float32) and DIR/decoded.npy (the decoded array, in its
+own precision).  The files stay under 64 MB together: the stream is written
+whole if that takes at most 60 % of it (the headline's does), and an output
+beyond its share as a fixed sample of its elements (the same seeded indices
+every run, sorted).
+The input is a function of the arguments alone, so two builds run with the
+same arguments can be compared output for output.
 
 With --gpus N > 1 and no launcher around it (WORLD_SIZE unset), bench.py
 starts its N ranks itself through torch.distributed.run before touching the
@@ -21,6 +41,8 @@ timed region, and reported under "allgather".
 
 Prints one JSON line on rank 0 (the driver contract), with
   value       = input GB/s of all ranks (10^9 B of input / s)
+  ms_per_step = wall milliseconds of one timed step
+and, with --full,
   roofline    = the dominant kernel's algorithmic bytes / its mean duration,
                 over the MI355X HBM3E peak (8.0 TB/s, MI355X_MICROARCH.md)
   cpu_baseline= the reference's own CPU zfp 0.5.0 (oracle/_ref), timed here
@@ -76,6 +98,14 @@ def parse():
     p.add_argument("--rate", type=float, default=8.0)
     p.add_argument("--dtype", default="float32", choices=["float32", "float64"])
     p.add_argument("--field", default="polynomial", choices=["polynomial", "splitmix"])
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: per-kernel times and roofline, the copy "
+                        "calibrator, the stream all-gather, BASELINE's other configurations, the host path, the CPU "
+                        "baseline and the parity checks against the reference's digests (the --no-* options "
+                        "trim this set)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs as DIR/stream.npy and DIR/decoded.npy "
+                        "(float32 / float64, a fixed seeded sample of an output beyond its share of 64 MB)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-host-path", action="store_true")
     p.add_argument("--no-copy-probe", action="store_true", help="skip the device-to-device copy bandwidth probe")
@@ -212,22 +242,78 @@ def dry_run(args):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    back = None
     for _ in range(args.steps):
-        step()
+        back = step()
     if world > 1:
         dist.barrier()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     info = rank_info(dist, world, dev, "gloo" if world > 1 else "none")
+    dumped = None
+    if args.dump_outputs and back is not None:
+        dumped = dump_outputs(args.dump_outputs, oracle.restatement.compress(a, mb).view(np.int64), back,
+                              f"_rank{rank}" if world > 1 else "")
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": round(a.nbytes * world * args.steps / float(t) / 1e9, 6),
                           "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                          "ms_per_step": round(float(t) * 1e3 / max(args.steps, 1), 4),
                           "data": "dry run: CPU oracle on a 16^3 slab per rank, not a measurement",
-                          **info}), flush=True)
+                          "dumped": dumped, **info}), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # all of --dump-outputs' files together (under 64 MB with their headers)
+DUMP_SEED = 20240229
+
+
+def sample_indices(n: int, k: int, seed: int = DUMP_SEED) -> np.ndarray | None:
+    """The fixed sample of an n-element output that --dump-outputs writes: None
+    (every element) if n <= k, else k sorted indices drawn with a seeded
+    generator -- the same ones for the same (n, k) in every run and build."""
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=k, dtype=np.int64))
+
+
+def stream_pieces(words: np.ndarray) -> np.ndarray:
+    """The stream's 64-bit words as their 16-bit pieces, least significant
+    first, in float32 (every piece exact): a .npy of floats that differs
+    wherever two streams differ in a bit."""
+    return np.ascontiguousarray(words).view(np.uint64).view("<u2").astype(np.float32)
+
+
+def dump_outputs(outdir: str, words, y, suffix: str = "") -> dict:
+    """Write the step's two outputs (torch tensors or numpy arrays: the int64
+    stream words and the decoded array) as outdir/stream<suffix>.npy and
+    outdir/decoded<suffix>.npy, together within DUMP_BUDGET_BYTES: the stream
+    gets what it needs up to 60 % of it (the headline's 16 MiB stream is written
+    whole), the decoded array the rest."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    w_share = min(16 * int(np.prod(words.shape)), DUMP_BUDGET_BYTES * 6 // 10)
+    d_share = DUMP_BUDGET_BYTES - w_share
+
+    def take(t, k):
+        flat = (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))).reshape(-1)
+        idx = sample_indices(flat.numel(), k)
+        if idx is not None:
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.cpu().numpy(), idx is not None
+
+    w, w_sampled = take(words, w_share // 16)  # a word is four float32 pieces
+    d, d_sampled = take(y, d_share // np.dtype(str(y.dtype).replace("torch.", "")).itemsize)
+    if not d_sampled:
+        d = d.reshape(tuple(y.shape))
+    files = {}
+    for name, arr, sampled in (("stream", stream_pieces(w), w_sampled), ("decoded", d, d_sampled)):
+        assert arr.dtype in (np.float32, np.float64)
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), arr)
+        files[f"{name}{suffix}.npy"] = {"dtype": str(arr.dtype), "values": int(arr.size), "sampled": sampled}
+    return files
 
 
 def cpu_share() -> tuple[int, int]:
@@ -648,10 +734,11 @@ def main():
     # the reference's own zfp 0.5.0 output (tests/golden/golden.json)
     step()
     torch.cuda.synchronize()
-    max_err = float((y.double() - x.double()).abs().max().item())
-    # Order of the GPU work.  The other GPU measurements of the line (BASELINE
-    # configs[4], the copy calibrator, the RCCL all-gather, per-kernel times) run
-    # before the timed region, with every graph captured up front and every
+    max_err = float((y.double() - x.double()).abs().max().item()) if args.full else None
+    # Order of the GPU work (--full; a plain run keeps only the last ~100 ms of
+    # it, as untimed replays of the step's graph, then the timed region).
+    # The other GPU measurements of the line (BASELINE configs[4], the copy
+    # calibrator, the RCCL all-gather, per-kernel times) run before the timed region, with every graph captured up front and every
     # host-side check (stream hashes, the CPU baseline) after it, so that the
     # timed steps start on a GPU that has been busy up to that point: after the
     # GPU idles (a host-side hash of the 1 GiB configs[4] stream takes seconds)
@@ -664,13 +751,14 @@ def main():
         raise SystemExit(f"--per-graph {per_graph} does not divide --steps {args.steps}")
     run = graphed(step, per_graph)
     run()  # the graph's first replay uploads it: never inside the timed region
-    enc_graph = graphed(lambda: cz.encode(x, maxbits, out=words), 50)
-    dec_graph = graphed(lambda: cz.decode(words, shape, x.dtype, maxbits, out=y), 50)
-    enc_graph()
-    dec_graph()
+    if args.full:
+        enc_graph = graphed(lambda: cz.encode(x, maxbits, out=words), 50)
+        dec_graph = graphed(lambda: cz.decode(words, shape, x.dtype, maxbits, out=y), 50)
+        enc_graph()
+        dec_graph()
 
     c5 = None
-    if not args.no_config5 and dims == 3 and args.dtype == "float32" and not strong:
+    if args.full and not args.no_config5 and dims == 3 and args.dtype == "float32" and not strong:
         try:
             c5 = run_config5(args.config5_edge, args.config5_steps, world, rank, dev, graphed, dist, use_dist)
         except torch.cuda.OutOfMemoryError as e:  # pragma: no cover
@@ -721,7 +809,7 @@ def main():
         return round(2 * nbytes / (ms * 1e-3) / 1e9, 1)
 
     hbm_copy = None
-    if rank == 0 and not args.no_copy_probe:
+    if args.full and rank == 0 and not args.no_copy_probe:
         hbm_copy = {"kernel": "cuzfp_hip_copy (16-B non-temporal loads/stores, one per lane, one grid)",
                     "GBps_1GiB": copy_GBps(1 << 30, "cuzfp"), "GBps_at_input_size": copy_GBps(a.nbytes, "cuzfp"),
                     "torch_copy_GBps_1GiB": copy_GBps(1 << 30, "torch"), "input_bytes": a.nbytes,
@@ -730,7 +818,7 @@ def main():
 
     # optional RCCL all-gather of the compressed stream (the exchange step)
     allgather = None
-    if use_dist and zd.uniform_shard_ok(gshape, world, maxbits):
+    if args.full and use_dist and zd.uniform_shard_ok(gshape, world, maxbits):
         full = allgather_words(zd, words)
         torch.cuda.synchronize()
         dist.barrier()
@@ -767,11 +855,20 @@ def main():
             warm_rest()
 
     t_pre = time.perf_counter()
-    enc_ms, enc_n = time_kernel(enc_graph, args.kernel_ms)
-    dec_ms, dec_n = time_kernel(dec_graph, args.kernel_ms, then=warmup)
-    pre_timed = {"what": "per-kernel timing (encode_ms, decode_ms): back-to-back hipGraph replays, then the W "
-                         "warmup steps", "encode_launches": enc_n, "decode_launches": dec_n,
-                 "wall_ms": round((time.perf_counter() - t_pre) * 1e3, 1)}
+    if args.full:
+        enc_ms, enc_n = time_kernel(enc_graph, args.kernel_ms)
+        dec_ms, dec_n = time_kernel(dec_graph, args.kernel_ms, then=warmup)
+        pre_timed = {"what": "per-kernel timing (encode_ms, decode_ms): back-to-back hipGraph replays, then the W "
+                             "warmup steps", "encode_launches": enc_n, "decode_launches": dec_n,
+                     "wall_ms": round((time.perf_counter() - t_pre) * 1e3, 1)}
+    else:
+        # a plain run measures no kernel on its own, but its timed steps start in
+        # the same state: the same GPU time of the step's own graph, untimed,
+        # with the warmup steps queued behind it
+        _, ramp_n = time_kernel(run, 2 * args.kernel_ms, then=warmup)
+        pre_timed = {"what": "clock ramp: back-to-back replays of the step's hipGraph (nothing measured), then "
+                             "the W warmup steps", "step_launches": ramp_n // 50 * per_graph,
+                     "wall_ms": round((time.perf_counter() - t_pre) * 1e3, 1)}
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -795,9 +892,15 @@ def main():
     # BASELINE configs[2] and configs[3] (N=1, headline run only), on the GPU
     # right after the timed region; their hashes with the other host checks
     others = None
-    if (world == 1 and not strong and not args.no_configs and dims == 3 and args.dtype == "float32"
+    if (args.full and world == 1 and not strong and not args.no_configs and dims == 3 and args.dtype == "float32"
             and n == 256 and args.rate == 8.0 and args.field == "polynomial"):
         others = run_other_configs(dev, graphed, stream)
+
+    # the last timed step's outputs, as its caller holds them (nothing after the
+    # timed region writes words or y)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, words, y, f"_rank{rank}" if world > 1 else "")
 
     # host-side checks, after the timed region: the stream's SHA-256 against the
     # reference's (N=1; the timed steps rewrote the same words), configs[4]'s parity
@@ -806,7 +909,7 @@ def main():
     key = {(3, 256, "float32", 8.0): "baseline/3d_f32_256_r8", (3, 256, "float64", 16.0): "baseline/3d_f64_256_r16",
            (2, 8192, "float32", 2.0): "baseline/2d_f32_8192_r2",
            (1, 1048576, "float32", 8.0): "baseline/1d_f32_1M_r8"}.get((dims, n, args.dtype, float(args.rate)))
-    if key and world == 1 and not strong and os.path.exists(gpath):
+    if args.full and key and world == 1 and not strong and os.path.exists(gpath):
         rec = json.load(open(gpath))["cases"].get(f"{key}/{args.field}")
         if rec:
             got = hashlib.sha256(words.cpu().numpy().tobytes()).hexdigest()
@@ -827,16 +930,17 @@ def main():
     s_bytes = nbytes_stream
     enc_bytes = n_in + s_bytes     # read array, write stream
     dec_bytes = s_bytes + n_in     # read stream, write array
-    dominant = "encode" if enc_ms >= dec_ms else "decode"
-    dom_ms = max(enc_ms, dec_ms)
-    dom_bytes = enc_bytes if dominant == "encode" else dec_bytes
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+    if args.full:
+        dominant = "encode" if enc_ms >= dec_ms else "decode"
+        dom_ms = max(enc_ms, dec_ms)
+        dom_bytes = enc_bytes if dominant == "encode" else dec_bytes
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
     workload = f"{dims}d_{args.dtype}_{n}^{dims}_rate{args.rate:g}" + (f"_zslab{world}" if strong and world > 1 else "")
     # roofline.traffic: HBM bytes a launch from rocprofv3 PMC counters, which a
     # run cannot collect on itself (a --pmc pass is its own profiled run): read
     # from the builder's PMC session record for this workload, and say which
     traffic, traffic_source = None, None
-    if os.path.exists(args.traffic_json):
+    if args.full and os.path.exists(args.traffic_json):
         try:
             tj = json.load(open(args.traffic_json))
             wk = workload
@@ -853,7 +957,7 @@ def main():
     result = None
     if rank == 0:
         host_path = None
-        if world == 1 and not args.no_host_path and not strong:
+        if args.full and world == 1 and not args.no_host_path and not strong:
             hp_in = torch.from_numpy(a).pin_memory().numpy()
             hp_out = torch.empty(s_bytes // 8, dtype=torch.int64).pin_memory().numpy().view(np.uint64)
             hp_back = torch.empty(a.shape, dtype=x.dtype).pin_memory().numpy()
@@ -906,7 +1010,7 @@ def main():
                                  "array bytes / max(array/h2d, stream/d2h), decompress array bytes / "
                                  "max(array/d2h, stream/h2d); H2D beside D2H run at ~48 GB/s each "
                                  "(profiles/r05_copy_chunks.txt), so ~0.95 is the practical ceiling"}
-        cpu = None if (args.no_cpu_baseline or world > 1 or strong) else cpu_baseline(a, maxbits)
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1 or strong) else cpu_baseline(a, maxbits)
         result = {
             "metric": METRIC if (dims == 3 and args.dtype == "float32") else
                       METRIC_OTHER.format(dims=dims, dt="f32" if args.dtype == "float32" else "f64"),
@@ -926,26 +1030,31 @@ def main():
                        "parallelism": f"z-slab x{world}", "stream_bytes_per_gpu": s_bytes},
             "pct_hbm_peak": round(100.0 * value / world * (enc_bytes + dec_bytes) / n_in / HBM_PEAK_GBS, 2),
             "gpu_ms_per_step": round(gpu_ms_per_step, 4),
-            "encode_ms": round(enc_ms, 4),
-            "decode_ms": round(dec_ms, 4),
-            "encode_GBps_input": round(n_in / (enc_ms * 1e-3) / 1e9, 1),
-            "decode_GBps_input": round(n_in / (dec_ms * 1e-3) / 1e9, 1),
-            "roofline": {"bound": "hbm", "kernel": f"zfp_{dominant}", "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": dom_bytes,
-                         "frac_of_copy": round(achieved / hbm_copy["GBps_1GiB"], 4) if hbm_copy else None},
-            "hbm_copy": hbm_copy,
-            "cpu_baseline": cpu,
-            "host_path": host_path,
-            "allgather": allgather,
-            "config5": config5,
-            "configs": configs,
-            "max_abs_err": max_err,
-            "parity": parity,
+            "full": args.full,
+            "dumped": dumped,
             "pre_timed_gpu_work": pre_timed,
             **ranks,
         }
+        if args.full:
+            result.update({
+                "encode_ms": round(enc_ms, 4),
+                "decode_ms": round(dec_ms, 4),
+                "encode_GBps_input": round(n_in / (enc_ms * 1e-3) / 1e9, 1),
+                "decode_GBps_input": round(n_in / (dec_ms * 1e-3) / 1e9, 1),
+                "roofline": {"bound": "hbm", "kernel": f"zfp_{dominant}", "achieved": round(achieved, 1),
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                             "traffic": traffic, "traffic_source": traffic_source,
+                             "algorithmic_bytes_per_launch": dom_bytes,
+                             "frac_of_copy": round(achieved / hbm_copy["GBps_1GiB"], 4) if hbm_copy else None},
+                "hbm_copy": hbm_copy,
+                "cpu_baseline": cpu,
+                "host_path": host_path,
+                "allgather": allgather,
+                "config5": config5,
+                "configs": configs,
+                "max_abs_err": max_err,
+                "parity": parity,
+            })
         print(json.dumps(result), flush=True)
     if use_dist:
         dist.barrier()

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 for sz in ${SIZES:-192 256 320 384 512 768}; do
   for p in 1 0 auto; do
     if [ "$p" = auto ]; then unset CUZFP_PRIO; else export CUZFP_PRIO=$p; fi
-    timeout -k 10 300 python bench.py --size "$sz" --steps 20 --warmup 5 --no-cpu-baseline --no-host-path \
+    timeout -k 10 300 python bench.py --full --size "$sz" --steps 20 --warmup 5 --no-cpu-baseline --no-host-path \
       > "$OUT/prio_${sz}_$p.json" 2>/dev/null || { echo "size $sz prio $p failed"; exit 1; }
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], sys.argv[3], d['value'], d['encode_ms'], d['decode_ms'], d['max_abs_err'])" \
       "$OUT/prio_${sz}_$p.json" "$sz" "$p"

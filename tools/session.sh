@@ -68,22 +68,22 @@ for s in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_${TAG}.log" 2>&1
       stop_on $? smoke; tail -2 "$OUT/smoke_${TAG}.log" ;;
     bench)
-      timeout -k 10 600 python bench.py --steps 20 --warmup 5 > "$OUT/bench_${TAG}.json" 2> "$OUT/bench_${TAG}.err"
+      timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_${TAG}.json" 2> "$OUT/bench_${TAG}.err"
       stop_on $? bench; tail -c 1500 "$OUT/bench_${TAG}.json" ;;
     bench200)
-      timeout -k 10 600 python bench.py --no-cpu-baseline --no-host-path > "$OUT/bench200_${TAG}.json" 2> "$OUT/bench200_${TAG}.err"
+      timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-host-path > "$OUT/bench200_${TAG}.json" 2> "$OUT/bench200_${TAG}.err"
       stop_on $? bench200; python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('value', d['value'], 'enc', d['encode_ms'], 'dec', d['decode_ms'], d['parity'], 'c5', (d.get('config5') or {}).get('value_GBps'))" "$OUT/bench200_${TAG}.json" ;;
     benchcfg)
-      timeout -k 10 300 python bench.py --dtype float64 --rate 16 --no-cpu-baseline --no-host-path --no-config5 > "$OUT/bench_f64_${TAG}.json" 2>&1
+      timeout -k 10 300 python bench.py --full --dtype float64 --rate 16 --no-cpu-baseline --no-host-path --no-config5 > "$OUT/bench_f64_${TAG}.json" 2>&1
       stop_on $? bench64; tail -1 "$OUT/bench_f64_${TAG}.json" | cut -c1-700
-      timeout -k 10 300 python bench.py --dims 2 --size 8192 --rate 2 --no-cpu-baseline --no-host-path --no-config5 > "$OUT/bench_2d_${TAG}.json" 2>&1
+      timeout -k 10 300 python bench.py --full --dims 2 --size 8192 --rate 2 --no-cpu-baseline --no-host-path --no-config5 > "$OUT/bench_2d_${TAG}.json" 2>&1
       stop_on $? bench2d; tail -1 "$OUT/bench_2d_${TAG}.json" | cut -c1-700
-      timeout -k 10 300 python bench.py --dims 1 --size 1048576 --rate 8 --no-cpu-baseline --no-host-path --no-config5 > "$OUT/bench_1d_${TAG}.json" 2>&1
+      timeout -k 10 300 python bench.py --full --dims 1 --size 1048576 --rate 8 --no-cpu-baseline --no-host-path --no-config5 > "$OUT/bench_1d_${TAG}.json" 2>&1
       stop_on $? bench1d; tail -1 "$OUT/bench_1d_${TAG}.json" | cut -c1-700 ;;
     prof)
       rm -rf "$OUT/prof_${TAG}"
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}" -o run -- \
-        python bench.py --steps 20 --no-cpu-baseline --no-host-path > "$OUT/prof_bench_${TAG}.json" 2>&1
+        python bench.py --full --steps 20 --no-cpu-baseline --no-host-path > "$OUT/prof_bench_${TAG}.json" 2>&1
       stop_on $? prof
       find "$OUT/prof_${TAG}" -name "*kernel_stats.csv" -exec head -6 {} \; ;;
     pmc)
