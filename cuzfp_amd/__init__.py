@@ -20,7 +20,7 @@ import numpy as np
 __all__ = [
     "TYPE_INT32", "TYPE_INT64", "TYPE_FLOAT", "TYPE_DOUBLE", "CodecError",
     "library", "library_path", "rate_to_maxbits", "stream_bytes", "maximum_size",
-    "encode", "decode", "compress_host", "decompress_host", "type_code",
+    "encode", "decode", "decode_region", "compress_host", "decompress_host", "type_code",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -77,6 +77,8 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_encode.argtypes = [vp, i, u, u, u, ll, ll, ll, u, vp, sz, ctypes.POINTER(sz), vp]
     lib.cuzfp_hip_decode.restype = i
     lib.cuzfp_hip_decode.argtypes = [vp, sz, i, u, u, u, ll, ll, ll, u, vp, vp]
+    lib.cuzfp_hip_decode_region.restype = i
+    lib.cuzfp_hip_decode_region.argtypes = [vp, sz, i, u, u, u, u, u, u, u, u, u, u, ll, ll, ll, vp, vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -218,6 +220,40 @@ def decode(words, shape, dtype, maxbits: int, out=None, stream=None):
                                     nx, ny, nz, sx, sy, sz, maxbits, out.data_ptr(),
                                     _stream_handle(stream))
     _check("decode", rc)
+    return out
+
+
+def decode_region(words, shape, dtype, maxbits: int, origin, extent, out=None, stream=None):
+    """Decompress the box ``origin .. origin + extent`` (slowest first, like
+    `shape`) of the array a device stream holds into a new (or given, possibly
+    strided) CUDA tensor of shape `extent`.  Only the box's blocks are read and
+    decoded: fixed rate puts block b at bits [b * maxbits, (b + 1) * maxbits)."""
+    import torch
+    shape = tuple(int(s) for s in shape)
+    origin = tuple(int(o) for o in origin)
+    extent = tuple(int(e) for e in extent)
+    nx, ny, nz = _extents(shape)
+    if len(origin) != len(shape) or len(extent) != len(shape):
+        raise ValueError(f"decode_region: origin {origin} and extent {extent} must have "
+                         f"the rank of shape {shape}")
+    if any(o < 0 for o in origin) or any(e <= 0 for e in extent):
+        raise ValueError("decode_region: origin must be non-negative and extent positive")
+    if not words.is_cuda:
+        raise ValueError("decode_region: expects a device stream")
+    if out is None:
+        out = torch.empty(extent, dtype=dtype, device=words.device)
+    elif _broadcast(out):
+        raise ValueError("decode_region: out is a broadcast view (zero stride); its elements alias each other")
+    elif tuple(out.shape) != extent:
+        raise ValueError(f"decode_region: out has shape {tuple(out.shape)}, expected {extent}")
+    ox, oy, oz = _extents(origin)
+    ex, ey, ez = _extents(extent)
+    sx, sy, sz = _strides(out)
+    rc = library().cuzfp_hip_decode_region(words.data_ptr(), words.numel() * words.element_size(),
+                                           type_code(out.dtype), nx, ny, nz, maxbits,
+                                           ox, oy, oz, ex, ey, ez, sx, sy, sz, out.data_ptr(),
+                                           _stream_handle(stream))
+    _check("decode_region", rc)
     return out
 
 

@@ -22,8 +22,8 @@ static int make_problem(int type, unsigned nx, unsigned ny, unsigned nz, long lo
   const unsigned dims = nz ? 3 : ny ? 2 : 1;
   const unsigned ebits = type == CUZFP_TYPE_FLOAT ? 9 : type == CUZFP_TYPE_DOUBLE ? 12 : 1;
   // One wave's LDS image must fit a workgroup's LDS beside the tables: the
-  // decoder's (maxbits / 32 + 5 rows of 256 B + 12 KiB of chunk tables) takes
-  // 141 KiB at CUZFP_MAX_BITS (16,384) of gfx950's 160 KiB (the launchers
+  // decoder's (maxbits / 32 + 5 rows of 256 B + 16 KiB of chunk tables) takes
+  // 145 KiB at CUZFP_MAX_BITS (16,384) of gfx950's 160 KiB (the launchers
   // check the device's budget).  The cap is far above the most bits any block
   // can use (zfp's ZFP_MAX_BITS, 4,171: 3D double at full precision); past
   // that a stream is padding.
@@ -798,6 +798,41 @@ int cuzfp_hip_decode(const uint64_t* d_stream, size_t stream_bytes, int type, un
   if (!d_data || !d_stream) return CUZFP_ERROR_INVALID_ARGUMENT;
   if (stream_bytes < stream_bytes_of(p.g)) return CUZFP_ERROR_BUFFER_TOO_SMALL;
   return launch_decode(p, d_stream, d_data, 0, waves_of(p.g), stream);
+}
+
+int cuzfp_hip_decode_region(const uint64_t* d_stream, size_t stream_bytes, int type,
+                            unsigned nx, unsigned ny, unsigned nz, unsigned maxbits,
+                            unsigned ox, unsigned oy, unsigned oz,
+                            unsigned ex, unsigned ey, unsigned ez,
+                            long long sx, long long sy, long long sz,
+                            void* d_out, hipStream_t stream) {
+  Problem p;
+  int rc = make_problem(type, nx, ny, nz, 0, 0, 0, maxbits, &p);
+  if (rc) return rc;
+  if (!d_out || !d_stream) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // an unused dimension takes origin 0 and extent 0 (as ny, nz = 0)
+  if (p.dims < 2 && (oy || ey)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 3 && (oz || ez)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 2) ey = 1;
+  if (p.dims < 3) ez = 1;
+  // the box: not empty, inside the array
+  if (!ex || !ey || !ez) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ox >= p.g.nx || ex > p.g.nx - ox || oy >= p.g.ny || ey > p.g.ny - oy || oz >= p.g.nz ||
+      ez > p.g.nz - oz)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (stream_bytes < stream_bytes_of(p.g)) return CUZFP_ERROR_BUFFER_TOO_SMALL;
+  const Region r = make_region(p.g, ox, oy, oz, ex, ey, ez, sx, sy, sz);
+  // a block-aligned box into a contiguous, 16-byte aligned array: the row stores
+  const bool fast = (type == CUZFP_TYPE_FLOAT || type == CUZFP_TYPE_DOUBLE) &&
+                    !((ox | ex) & 3) && (p.dims < 2 || !((oy | ey) & 3)) &&
+                    (p.dims < 3 || !((oz | ez) & 3)) && r.sx == 1 && r.sy == (long long)ex &&
+                    r.sz == (long long)ex * ey && ((uintptr_t)d_out & 15) == 0;
+  switch (type) {
+    case CUZFP_TYPE_INT32: return launch_decode_region_type<int32_t>(p, r, d_stream, false, d_out, stream);
+    case CUZFP_TYPE_INT64: return launch_decode_region_type<int64_t>(p, r, d_stream, false, d_out, stream);
+    case CUZFP_TYPE_FLOAT: return launch_decode_region_type<float>(p, r, d_stream, fast, d_out, stream);
+    default: return launch_decode_region_type<double>(p, r, d_stream, fast, d_out, stream);
+  }
 }
 
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {

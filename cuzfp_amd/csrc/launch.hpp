@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/cuzfp_hip.h"
+#include "region.hpp"
 
 namespace cuzfp {
 
@@ -41,6 +42,36 @@ inline void set_divisor(uint32_t d, uint32_t& m, uint32_t& s) {
   m = (uint32_t)(((1ull << s) + d - 1) / d);
 }
 
+// The Region of a box inside the array of `g` (make_problem's: extents 1 along
+// unused dimensions), origin and extent likewise normalised (0 and 1 along an
+// unused dimension), the box inside the array and not empty; strides 0 =
+// contiguous out[ez][ey][ex].
+inline Region make_region(const Geometry& g, uint32_t ox, uint32_t oy, uint32_t oz, uint32_t ex,
+                          uint32_t ey, uint32_t ez, int64_t sx, int64_t sy, int64_t sz) {
+  Region r;
+  r.bx = g.bx;
+  r.by = g.by;
+  r.bx0 = ox / 4;
+  r.by0 = oy / 4;
+  r.bz0 = oz / 4;
+  r.rbx = (uint32_t)(((uint64_t)ox + ex + 3) / 4) - r.bx0;
+  r.rby = (uint32_t)(((uint64_t)oy + ey + 3) / 4) - r.by0;
+  r.rbz = (uint32_t)(((uint64_t)oz + ez + 3) / 4) - r.bz0;
+  const uint64_t n = (uint64_t)r.rbx * r.rby * r.rbz;  // <= nblocks
+  r.nrb = (uint32_t)n;
+  r.ox = ox; r.oy = oy; r.oz = oz;
+  r.ex = ex; r.ey = ey; r.ez = ez;
+  r.maxbits = g.maxbits;
+  set_divisor(r.rbx, r.drx_m, r.drx_s);
+  set_divisor(r.rbx * r.rby, r.drp_m, r.drp_s);
+  r.divmagic = n < (1ull << 31) ? 1u : 0u;
+  r.stream_dwords = (((uint64_t)g.nblocks * g.maxbits + 63) / 64) * 2;
+  r.sx = sx ? sx : 1;
+  r.sy = sy ? sy : (int64_t)ex;
+  r.sz = sz ? sz : (int64_t)ex * ey;
+  return r;
+}
+
 struct Problem {
   int type;
   unsigned dims;
@@ -56,5 +87,10 @@ int launch_encode_type(const Problem& p, const void* data, bool fast, uint64_t* 
 template <typename Scalar>
 int launch_decode_type(const Problem& p, const uint64_t* stream, bool fast, void* data,
                        uint32_t wave0, uint32_t nwaves, hipStream_t st);
+// The sub-box decoder (region_kernels.hpp): `out` is the box's element (0, 0, 0);
+// fast: a block-aligned box into a contiguous, 16-byte aligned `out`.
+template <typename Scalar>
+int launch_decode_region_type(const Problem& p, const Region& r, const uint64_t* stream, bool fast,
+                              void* out, hipStream_t st);
 
 }  // namespace cuzfp

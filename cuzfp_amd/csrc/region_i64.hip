@@ -1,0 +1,7 @@
+// cuzfp_amd/csrc/region_i64.hip -- int64_t instantiations of the sub-box decoder.
+#include "region_kernels.hpp"
+
+namespace cuzfp {
+template int launch_decode_region_type<int64_t>(const Problem&, const Region&, const uint64_t*, bool, void*,
+                                              hipStream_t);
+}  // namespace cuzfp

@@ -61,11 +61,11 @@ extern "C" {
  * (zfp_structs.h:12), the most bits any block can use; beyond that a stream is
  * padding.  The bound keeps one wave's LDS stream image within a gfx950
  * workgroup's LDS (160 KiB, hipDeviceAttributeMaxSharedMemoryPerBlock): the
- * decoder's image at 16384 bits is 129 KiB plus 12 KiB of tables.  On a device
- * with less LDS per workgroup (e.g. 64 KiB) the launchers check one wave's image
- * plus the tables against the device's budget before launching and return
- * CUZFP_ERROR_INVALID_ARGUMENT for a call that does not fit (3D f32/f64 past
- * about 6,500 bits on a 64 KiB device); the environment variable
+ * decoder's image at 16384 bits is 129 KiB plus 16 KiB of tables, 145 KiB.  On
+ * a device with less LDS per workgroup (e.g. 64 KiB) the launchers check one
+ * wave's image plus the tables against the device's budget before launching and
+ * return CUZFP_ERROR_INVALID_ARGUMENT for a call that does not fit (3D f32/f64
+ * past about 5,980 bits on a 64 KiB device); the environment variable
  * CUZFP_LDS_CAP_BYTES lowers the budget (tests). */
 #define CUZFP_MAX_BITS 16384
 
@@ -110,6 +110,23 @@ int cuzfp_hip_encode(const void* d_data, int type, unsigned nx, unsigned ny, uns
 int cuzfp_hip_decode(const uint64_t* d_stream, size_t stream_bytes, int type, unsigned nx,
                      unsigned ny, unsigned nz, long long sx, long long sy, long long sz,
                      unsigned maxbits, void* d_data, hipStream_t stream);
+
+/* Not a reference entry point (callers test CUZFP_HIP_HAS_DECODE_REGION): fixed
+ * rate puts block b at bits [b*maxbits, (b+1)*maxbits), so a box decodes from
+ * its own blocks alone.
+ * Decode the elements [ox, ox+ex) x [oy, oy+ey) x [oz, oz+ez) of the array that
+ * d_stream holds (nx, ny, nz, maxbits as for cuzfp_hip_decode) into d_out, an
+ * array of extent ex x ey x ez with element strides sx, sy, sz (0 = contiguous
+ * out[ez][ey][ex]; negative allowed).  Unused dimensions: origin 0, extent 0.
+ * CUZFP_ERROR_INVALID_ARGUMENT for an empty box or one that leaves the array;
+ * stream_bytes must cover the whole array's stream. */
+#define CUZFP_HIP_HAS_DECODE_REGION 1
+int cuzfp_hip_decode_region(const uint64_t* d_stream, size_t stream_bytes, int type,
+                            unsigned nx, unsigned ny, unsigned nz, unsigned maxbits,
+                            unsigned ox, unsigned oy, unsigned oz,
+                            unsigned ex, unsigned ey, unsigned ez,
+                            long long sx, long long sy, long long sz,
+                            void* d_out, hipStream_t stream);
 
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range

@@ -28,7 +28,7 @@ def build(variants=VARIANTS):
         d = os.path.join(OUT, f"p{v}")
         os.makedirs(d, exist_ok=True)
         objs = []
-        for u in ("inst_f32", "inst_f64", "inst_i32", "inst_i64", "capi"):
+        for u in b.KERNEL_UNITS:
             o = os.path.join(d, u + ".o")
             objs.append(o)
             procs.append(subprocess.Popen([b.HIPCC, *b.CXXFLAGS, f"-DCUZFP_PROBE={v}", "-c",
@@ -42,7 +42,7 @@ def build(variants=VARIANTS):
     assert all(p.returncode == 0 for p in procs)
     for v in variants:
         d = os.path.join(OUT, f"p{v}")
-        objs = [os.path.join(d, u + ".o") for u in ("inst_f32", "inst_f64", "inst_i32", "inst_i64", "capi")]
+        objs = [os.path.join(d, u + ".o") for u in b.KERNEL_UNITS]
         subprocess.check_call([b.HIPCC, f"--offload-arch={b.ARCH}", "-shared", "-fPIC", "-o",
                                os.path.join(d, "libcuzfp_hip.so"), *objs])
     print("built", OUT)

@@ -37,7 +37,8 @@ def _stub_objs(unit):
     hdrs = [os.path.join(b.CSRC, h) for h in b.HEADERS] + [os.path.join(b.INC, "cuzfp_hip.h")]
     objs, procs = [], []
     for u, flags in (("inst_f32", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("inst_f64", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]),
-                     ("inst_i32", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("inst_i64", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("capi", [])):
+                     ("inst_i32", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("inst_i64", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]),
+                     ("region_f32", []), ("region_f64", []), ("region_i32", []), ("region_i64", []), ("capi", [])):
         if u == unit:
             continue
         o = os.path.join(STUB, u + ".o")
