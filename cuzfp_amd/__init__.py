@@ -20,7 +20,7 @@ import numpy as np
 __all__ = [
     "TYPE_INT32", "TYPE_INT64", "TYPE_FLOAT", "TYPE_DOUBLE", "CodecError",
     "library", "library_path", "rate_to_maxbits", "stream_bytes", "maximum_size",
-    "encode", "decode", "decode_region", "compress_host", "decompress_host", "type_code",
+    "encode", "decode", "decode_region", "encode_region", "compress_host", "decompress_host", "type_code",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -79,6 +79,8 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_decode.argtypes = [vp, sz, i, u, u, u, ll, ll, ll, u, vp, vp]
     lib.cuzfp_hip_decode_region.restype = i
     lib.cuzfp_hip_decode_region.argtypes = [vp, sz, i, u, u, u, u, u, u, u, u, u, u, ll, ll, ll, vp, vp]
+    lib.cuzfp_hip_encode_region.restype = i
+    lib.cuzfp_hip_encode_region.argtypes = [vp, i, u, u, u, u, u, u, u, u, u, u, ll, ll, ll, vp, sz, vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -166,15 +168,10 @@ def _check_host_out(out: np.ndarray, shape, dtype, what: str) -> None:
         raise ValueError(f"{what}: out has shape {out.shape}, expected {tuple(shape)}")
 
 
-def encode(x, maxbits: int, out=None, stream=None):
-    """Compress a CUDA tensor; returns the stream as an int64 tensor of 64-bit words.
-
-    Bit-exact with zfp 0.5.0 fixed-rate mode (``zfp_compress`` with
-    minbits = maxbits).  Asynchronous on `stream` (default: torch's current).
-    """
+def _materialise(x, stream):
+    """A broadcast view (a zero stride means "contiguous" to the C-ABI) made
+    contiguous on the launch stream; any other tensor as it is."""
     import torch
-    if not x.is_cuda:
-        raise ValueError("encode: expects a device tensor (use compress_host for host arrays)")
     if _broadcast(x):
         # materialise a broadcast view (a zero stride means "contiguous" to the
         # C-ABI) on the launch stream, after the work already queued on torch's
@@ -190,6 +187,19 @@ def encode(x, maxbits: int, out=None, stream=None):
             x = src.contiguous()
         if s != cur:
             src.record_stream(s)
+    return x
+
+
+def encode(x, maxbits: int, out=None, stream=None):
+    """Compress a CUDA tensor; returns the stream as an int64 tensor of 64-bit words.
+
+    Bit-exact with zfp 0.5.0 fixed-rate mode (``zfp_compress`` with
+    minbits = maxbits).  Asynchronous on `stream` (default: torch's current).
+    """
+    import torch
+    if not x.is_cuda:
+        raise ValueError("encode: expects a device tensor (use compress_host for host arrays)")
+    x = _materialise(x, stream)
     t = type_code(x.dtype)
     nx, ny, nz = _extents(x.shape)
     nbytes = stream_bytes(x.shape, x.dtype, maxbits)
@@ -255,6 +265,44 @@ def decode_region(words, shape, dtype, maxbits: int, origin, extent, out=None, s
                                            _stream_handle(stream))
     _check("decode_region", rc)
     return out
+
+
+def encode_region(x, words, shape, maxbits: int, origin, stream=None):
+    """Write the box `x` (a device tensor whose shape is the box's extent) at
+    `origin` (slowest first, like `shape`) into `words`, the device stream of
+    an array of `shape` at `maxbits`, in place; returns `words`.
+
+    Only the box's blocks are re-coded; every other bit of the stream stays as
+    it was.  A block the box covers (all its elements inside the array lie in
+    the box) is coded from `x` alone.  A partially covered block is a
+    read-modify-write: it is decoded, the box's elements are replaced and the
+    block is encoded again, so its other elements may change within the rate's
+    error.  `x` may be strided; a broadcast view (fill the box with a constant)
+    is materialised on the launch stream as `encode` does.  Calls whose boxes
+    share a block must be ordered by the caller."""
+    shape = tuple(int(s) for s in shape)
+    origin = tuple(int(o) for o in origin)
+    extent = tuple(int(e) for e in getattr(x, "shape", ()))
+    nx, ny, nz = _extents(shape)
+    if len(origin) != len(shape) or len(extent) != len(shape):
+        raise ValueError(f"encode_region: origin {origin} and the box's shape {extent} must have "
+                         f"the rank of shape {shape}")
+    if any(o < 0 for o in origin) or any(e <= 0 for e in extent):
+        raise ValueError("encode_region: origin must be non-negative and the box not empty")
+    if any(o + e > n for o, e, n in zip(origin, extent, shape)):
+        raise ValueError(f"encode_region: the box {origin} + {extent} leaves the array {shape}")
+    if not x.is_cuda or not words.is_cuda:
+        raise ValueError("encode_region: expects a device box and a device stream")
+    x = _materialise(x, stream)
+    ox, oy, oz = _extents(origin)
+    ex, ey, ez = _extents(extent)
+    sx, sy, sz = _strides(x)
+    rc = library().cuzfp_hip_encode_region(x.data_ptr(), type_code(x.dtype), nx, ny, nz, maxbits,
+                                           ox, oy, oz, ex, ey, ez, sx, sy, sz, words.data_ptr(),
+                                           words.numel() * words.element_size(),
+                                           _stream_handle(stream))
+    _check("encode_region", rc)
+    return words
 
 
 def copy(src, dst, stream=None):

@@ -835,6 +835,40 @@ int cuzfp_hip_decode_region(const uint64_t* d_stream, size_t stream_bytes, int t
   }
 }
 
+int cuzfp_hip_encode_region(const void* d_box, int type,
+                            unsigned nx, unsigned ny, unsigned nz, unsigned maxbits,
+                            unsigned ox, unsigned oy, unsigned oz,
+                            unsigned ex, unsigned ey, unsigned ez,
+                            long long sx, long long sy, long long sz,
+                            uint64_t* d_stream, size_t stream_bytes, hipStream_t stream) {
+  Problem p;
+  int rc = make_problem(type, nx, ny, nz, 0, 0, 0, maxbits, &p);
+  if (rc) return rc;
+  if (!d_box || !d_stream) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the argument rules of cuzfp_hip_decode_region
+  if (p.dims < 2 && (oy || ey)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 3 && (oz || ez)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 2) ey = 1;
+  if (p.dims < 3) ez = 1;
+  if (!ex || !ey || !ez) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ox >= p.g.nx || ex > p.g.nx - ox || oy >= p.g.ny || ey > p.g.ny - oy || oz >= p.g.nz ||
+      ez > p.g.nz - oz)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (stream_bytes < stream_bytes_of(p.g)) return CUZFP_ERROR_BUFFER_TOO_SMALL;
+  const Region r = make_region(p.g, ox, oy, oz, ex, ey, ez, sx, sy, sz);
+  const bool covered = region_covered(p.g, r);
+  // a contiguous, 16-byte aligned box of whole blocks: the row loads
+  const bool rows = covered && !(ex & 3) && (p.dims < 2 || !(ey & 3)) && (p.dims < 3 || !(ez & 3)) &&
+                    r.sx == 1 && r.sy == (long long)ex && r.sz == (long long)ex * ey &&
+                    ((uintptr_t)d_box & 15) == 0;
+  switch (type) {
+    case CUZFP_TYPE_INT32: return launch_encode_region_type<int32_t>(p, r, d_box, covered, rows, d_stream, stream);
+    case CUZFP_TYPE_INT64: return launch_encode_region_type<int64_t>(p, r, d_box, covered, rows, d_stream, stream);
+    case CUZFP_TYPE_FLOAT: return launch_encode_region_type<float>(p, r, d_box, covered, rows, d_stream, stream);
+    default: return launch_encode_region_type<double>(p, r, d_box, covered, rows, d_stream, stream);
+  }
+}
+
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {
   if (!d_src || !d_dst || (bytes & 15) || (((uintptr_t)d_src | (uintptr_t)d_dst) & 15))
     return CUZFP_ERROR_INVALID_ARGUMENT;

@@ -93,4 +93,20 @@ template <typename Scalar>
 int launch_decode_region_type(const Problem& p, const Region& r, const uint64_t* stream, bool fast,
                               void* out, hipStream_t st);
 
+// Every block the box touches is covered: each of its elements that lies
+// inside the array lies inside the box.  Along an axis: the origin is a
+// multiple of 4 and the far side is one or the array's edge.
+inline bool region_covered(const Geometry& g, const Region& r) {
+  auto axis = [](uint32_t o, uint32_t e, uint32_t n) { return !(o & 3) && (!((o + e) & 3) || o + e == n); };
+  return axis(r.ox, r.ex, g.nx) && axis(r.oy, r.ey, g.ny) && axis(r.oz, r.ez, g.nz);
+}
+
+// The sub-box encoder (region_update_kernels.hpp): `box` is the box's element
+// (0, 0, 0), strides in the Region; covered: region_covered (else the
+// read-modify-write variant); rows: covered, and the box is contiguous,
+// 16-byte aligned and a whole number of blocks.
+template <typename Scalar>
+int launch_encode_region_type(const Problem& p, const Region& r, const void* box, bool covered, bool rows,
+                              uint64_t* stream, hipStream_t st);
+
 }  // namespace cuzfp

@@ -1,7 +1,8 @@
-// cuzfp_amd/csrc/region.hpp -- index and clip arithmetic of the sub-box decoder
-// (cuzfp_hip_decode_region), for host and device: the launcher fills a Region,
-// the kernel (region_kernels.hpp) and tests/native/region_map.cpp read it
-// through the same functions.
+// cuzfp_amd/csrc/region.hpp -- index, clip and store-span arithmetic of the
+// sub-box decoder and encoder (cuzfp_hip_decode_region, cuzfp_hip_encode_region),
+// for host and device: the launcher fills a Region, the kernels
+// (region_kernels.hpp, region_update_kernels.hpp) and tests/native/region_map.cpp,
+// region_store.cpp read it through the same functions.
 //
 // The box [ox, ox+ex) x [oy, oy+ey) x [oz, oz+ez) of an array of bx x by x bz
 // blocks covers the block columns [ox/4, (ox+ex+3)/4), likewise in y and z:
@@ -79,6 +80,39 @@ CUZFP_HD void region_block_bits(uint32_t b, uint32_t maxbits, uint64_t& dword, u
 CUZFP_HD bool region_in_stream(const Region& g, uint64_t d) { return d < g.stream_dwords; }
 CUZFP_HD uint64_t region_clamp(const Region& g, uint64_t d) {
   return d < g.stream_dwords ? d : g.stream_dwords - 1;
+}
+
+// The stream dwords block b's bits [b*maxbits, (b+1)*maxbits) occupy, for the
+// sub-box encoder's stores (region_update_kernels.hpp): a head dword the block
+// shares with the block before it (head_mask: the block's bits in it; 0 when
+// the block starts on a dword boundary), `nwhole` dwords from `whole` on that
+// hold the block's bits only, and a tail dword shared with the block after it
+// or with the stream's padding (tail_mask; 0 when the block ends on a dword
+// boundary or inside its head dword).  A block of fewer than 32 bits that
+// starts on a dword boundary has only a tail.  head, the whole dwords and tail
+// are consecutive; every one of them holds a bit of the block, so none is at
+// or past the stream's end.
+struct RegionSpan {
+  uint64_t head, whole, tail;  // dword indices
+  uint32_t head_mask, nwhole, tail_mask;
+};
+
+CUZFP_HD RegionSpan region_span(uint32_t b, uint32_t maxbits) {
+  RegionSpan s;
+  uint32_t s0;
+  region_block_bits(b, maxbits, s.head, s0);
+  const uint64_t end = (uint64_t)b * maxbits + maxbits;
+  const uint32_t t = (uint32_t)end & 31u;
+  s.tail = end >> 5;
+  s.whole = s.head + (s0 ? 1u : 0u);
+  s.head_mask = 0;
+  if (s0) {
+    s.head_mask = ~0u << s0;
+    if (s.tail == s.head) s.head_mask &= (1u << t) - 1u;  // the block ends in its head dword
+  }
+  s.nwhole = s.tail > s.whole ? (uint32_t)(s.tail - s.whole) : 0u;
+  s.tail_mask = (t && (s.tail > s.head || !s0)) ? (1u << t) - 1u : 0u;
+  return s;
 }
 
 // Array coordinate c along an axis with box origin o and extent e: inside the

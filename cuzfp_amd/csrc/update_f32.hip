@@ -1,0 +1,7 @@
+// cuzfp_amd/csrc/update_f32.hip -- float instantiations of the sub-box encoder.
+#include "region_update_kernels.hpp"
+
+namespace cuzfp {
+template int launch_encode_region_type<float>(const Problem&, const Region&, const void*, bool, bool, uint64_t*,
+                                            hipStream_t);
+}  // namespace cuzfp

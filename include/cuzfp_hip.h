@@ -128,6 +128,46 @@ int cuzfp_hip_decode_region(const uint64_t* d_stream, size_t stream_bytes, int t
                             long long sx, long long sy, long long sz,
                             void* d_out, hipStream_t stream);
 
+/* Not a reference entry point (callers test CUZFP_HIP_HAS_ENCODE_REGION): the
+ * write half of cuzfp_hip_decode_region.  Write the box [ox, ox+ex) x
+ * [oy, oy+ey) x [oz, oz+ez) of new values into the existing stream d_stream of
+ * an nx x ny x nz array at maxbits, in place.  d_box is element (0, 0, 0) of
+ * the box, an array of extent ex x ey x ez with element strides sx, sy, sz
+ * (0 = contiguous box[ez][ey][ex]; negative allowed).  Arguments and status
+ * codes are those of cuzfp_hip_decode_region; stream_bytes must cover the whole
+ * array's stream.
+ *
+ * Every block the box touches is re-coded and replaces its bits
+ * [b*maxbits, (b+1)*maxbits); every other bit of the stream, the other blocks
+ * and the zero padding after the last one, stays exactly as it was.
+ *  - A block whose elements inside the array all lie inside the box (a box
+ *    that reaches the array's far edge covers that edge's partial blocks) is
+ *    coded from the box's values, elements outside the array padded from them
+ *    as cuzfp_hip_encode pads.  Its old bits are not read.
+ *  - A partially covered block is a read-modify-write: its old bits are
+ *    decoded as cuzfp_hip_decode_region decodes them, the elements inside the
+ *    box are replaced, and the result is encoded.  THE BLOCK'S OTHER ELEMENTS
+ *    ARE RE-ENCODED FROM THEIR DECODED VALUES AND MAY THEREFORE CHANGE WITHIN
+ *    THE RATE'S ERROR.  A block-aligned box (or one aligned at its origin and
+ *    ending at the array's edges) touches no such block.
+ * The result equals encoding the whole array after pasting the box into the
+ * stream's decode, restricted to the bits of the box's blocks.
+ *
+ * Asynchronous on `stream`: one kernel launch, no allocation, no
+ * synchronisation; it can be captured into a hipGraph.  d_box must not
+ * overlap the stream.  Calls whose boxes share no block may run concurrently
+ * (on different streams); calls that share a block must be ordered by the
+ * caller.  CUZFP_ERROR_INVALID_ARGUMENT also when one wave's block images and
+ * tables exceed the device's LDS per workgroup (see CUZFP_MAX_BITS; on gfx950
+ * every maxbits fits). */
+#define CUZFP_HIP_HAS_ENCODE_REGION 1
+int cuzfp_hip_encode_region(const void* d_box, int type,
+                            unsigned nx, unsigned ny, unsigned nz, unsigned maxbits,
+                            unsigned ox, unsigned oy, unsigned oz,
+                            unsigned ex, unsigned ey, unsigned ez,
+                            long long sx, long long sy, long long sz,
+                            uint64_t* d_stream, size_t stream_bytes, hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,
