@@ -20,7 +20,7 @@ import numpy as np
 __all__ = [
     "TYPE_INT32", "TYPE_INT64", "TYPE_FLOAT", "TYPE_DOUBLE", "CodecError",
     "library", "library_path", "rate_to_maxbits", "stream_bytes", "maximum_size",
-    "encode", "decode", "decode_region", "encode_region", "compress_host", "decompress_host", "type_code",
+    "encode", "decode", "decode_region", "encode_region", "truncate", "compress_host", "decompress_host", "type_code",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -79,6 +79,10 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_decode.argtypes = [vp, sz, i, u, u, u, ll, ll, ll, u, vp, vp]
     lib.cuzfp_hip_decode_region.restype = i
     lib.cuzfp_hip_decode_region.argtypes = [vp, sz, i, u, u, u, u, u, u, u, u, u, u, ll, ll, ll, vp, vp]
+    lib.cuzfp_hip_decode_region_prefix.restype = i
+    lib.cuzfp_hip_decode_region_prefix.argtypes = [vp, sz, i, u, u, u, u, u, u, u, u, u, u, u, ll, ll, ll, vp, vp]
+    lib.cuzfp_hip_truncate.restype = i
+    lib.cuzfp_hip_truncate.argtypes = [vp, sz, i, u, u, u, u, u, vp, sz, ctypes.POINTER(sz), vp]
     lib.cuzfp_hip_encode_region.restype = i
     lib.cuzfp_hip_encode_region.argtypes = [vp, i, u, u, u, u, u, u, u, u, u, u, ll, ll, ll, vp, sz, vp]
     lib.cuzfp_hip_compress_host.restype = i
@@ -214,9 +218,18 @@ def encode(x, maxbits: int, out=None, stream=None):
     return out
 
 
-def decode(words, shape, dtype, maxbits: int, out=None, stream=None):
-    """Decompress a device stream (int64 words) into a new (or given) CUDA tensor."""
+def decode(words, shape, dtype, maxbits: int, out=None, stream=None, prefix_bits=None):
+    """Decompress a device stream (int64 words) into a new (or given) CUDA tensor.
+
+    `prefix_bits` (<= maxbits) decodes only the first prefix_bits of each block,
+    which sit `maxbits` apart: the array the stream truncated to prefix_bits
+    holds (see `truncate`), through `decode_region` with the whole array as
+    the box.  None decodes every block in full."""
     import torch
+    if prefix_bits is not None:
+        shape = tuple(int(s) for s in (shape if out is None else out.shape))
+        return decode_region(words, shape, dtype, maxbits, (0,) * len(shape), shape, out=out,
+                             stream=stream, prefix_bits=prefix_bits)
     if not words.is_cuda:
         raise ValueError("decode: expects a device stream")
     if out is None:
@@ -233,11 +246,16 @@ def decode(words, shape, dtype, maxbits: int, out=None, stream=None):
     return out
 
 
-def decode_region(words, shape, dtype, maxbits: int, origin, extent, out=None, stream=None):
+def decode_region(words, shape, dtype, maxbits: int, origin, extent, out=None, stream=None,
+                  prefix_bits=None):
     """Decompress the box ``origin .. origin + extent`` (slowest first, like
     `shape`) of the array a device stream holds into a new (or given, possibly
     strided) CUDA tensor of shape `extent`.  Only the box's blocks are read and
-    decoded: fixed rate puts block b at bits [b * maxbits, (b + 1) * maxbits)."""
+    decoded: fixed rate puts block b at bits [b * maxbits, (b + 1) * maxbits).
+
+    `prefix_bits` (<= maxbits) decodes each block from its first prefix_bits
+    alone: bit for bit what `decode_region` at prefix_bits gives on
+    ``truncate(words, ..., prefix_bits)``, without making that stream."""
     import torch
     shape = tuple(int(s) for s in shape)
     origin = tuple(int(o) for o in origin)
@@ -248,6 +266,9 @@ def decode_region(words, shape, dtype, maxbits: int, origin, extent, out=None, s
                          f"the rank of shape {shape}")
     if any(o < 0 for o in origin) or any(e <= 0 for e in extent):
         raise ValueError("decode_region: origin must be non-negative and extent positive")
+    if prefix_bits is not None and prefix_bits > maxbits:
+        raise ValueError(f"decode_region: prefix_bits {prefix_bits} exceeds maxbits {maxbits}; a block holds "
+                         "no more than maxbits bits")
     if not words.is_cuda:
         raise ValueError("decode_region: expects a device stream")
     if out is None:
@@ -259,11 +280,49 @@ def decode_region(words, shape, dtype, maxbits: int, origin, extent, out=None, s
     ox, oy, oz = _extents(origin)
     ex, ey, ez = _extents(extent)
     sx, sy, sz = _strides(out)
-    rc = library().cuzfp_hip_decode_region(words.data_ptr(), words.numel() * words.element_size(),
-                                           type_code(out.dtype), nx, ny, nz, maxbits,
-                                           ox, oy, oz, ex, ey, ez, sx, sy, sz, out.data_ptr(),
-                                           _stream_handle(stream))
+    if prefix_bits is None:
+        rc = library().cuzfp_hip_decode_region(words.data_ptr(), words.numel() * words.element_size(),
+                                               type_code(out.dtype), nx, ny, nz, maxbits,
+                                               ox, oy, oz, ex, ey, ez, sx, sy, sz, out.data_ptr(),
+                                               _stream_handle(stream))
+    else:
+        rc = library().cuzfp_hip_decode_region_prefix(words.data_ptr(), words.numel() * words.element_size(),
+                                                      type_code(out.dtype), nx, ny, nz, maxbits, prefix_bits,
+                                                      ox, oy, oz, ex, ey, ez, sx, sy, sz, out.data_ptr(),
+                                                      _stream_handle(stream))
     _check("decode_region", rc)
+    return out
+
+
+def truncate(words, shape, dtype, maxbits: int, new_maxbits: int, out=None, stream=None):
+    """The stream of the same array at `new_maxbits` <= `maxbits` bits a block,
+    cut from the device stream `words` (int64 words) at `maxbits` without
+    decoding: every block's first new_maxbits bits, packed new_maxbits apart.
+
+    zfp's coder is embedded, so the result is byte for byte what `encode` of the
+    original array gives at new_maxbits.  Returns an int64 word tensor
+    (allocated when `out` is None; `out` may be longer than the stream, its
+    words past the stream are left alone, and it must not overlap `words`).
+    Widening is not offered: blocks zero-padded to a higher rate are not the
+    same stream as encoding at that rate, and do not decode to the same values."""
+    import torch
+    if new_maxbits > maxbits:
+        raise ValueError(f"truncate: new_maxbits {new_maxbits} exceeds maxbits {maxbits}; widening is not "
+                         "supported, zero-padded blocks are not the same stream as encoding at the higher rate")
+    if not words.is_cuda:
+        raise ValueError("truncate: expects a device stream")
+    nx, ny, nz = _extents(shape)
+    nbytes = stream_bytes(shape, dtype, new_maxbits)
+    if out is None:
+        out = torch.empty(nbytes // 8, dtype=torch.int64, device=words.device)
+    elif not out.is_cuda or not out.is_contiguous():
+        raise ValueError("truncate: out must be a contiguous device tensor")
+    got = ctypes.c_size_t(0)
+    rc = library().cuzfp_hip_truncate(words.data_ptr(), words.numel() * words.element_size(), type_code(dtype),
+                                      nx, ny, nz, maxbits, new_maxbits, out.data_ptr(),
+                                      out.numel() * out.element_size(), ctypes.byref(got),
+                                      _stream_handle(stream))
+    _check("truncate", rc)
     return out
 
 

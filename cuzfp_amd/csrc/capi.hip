@@ -15,12 +15,15 @@ namespace cuzfp {
 
 thread_local int t_last_hip = hipSuccess;
 
+// the least bits a block takes: a float's or double's exponent and the zero flag
+static unsigned min_bits(int type) { return type == CUZFP_TYPE_FLOAT ? 9 : type == CUZFP_TYPE_DOUBLE ? 12 : 1; }
+
 static int make_problem(int type, unsigned nx, unsigned ny, unsigned nz, long long sx,
                         long long sy, long long sz, unsigned maxbits, Problem* pr) {
   if (type < CUZFP_TYPE_INT32 || type > CUZFP_TYPE_DOUBLE) return CUZFP_ERROR_UNSUPPORTED_TYPE;
   if (!nx || (nz && !ny)) return CUZFP_ERROR_INVALID_ARGUMENT;
   const unsigned dims = nz ? 3 : ny ? 2 : 1;
-  const unsigned ebits = type == CUZFP_TYPE_FLOAT ? 9 : type == CUZFP_TYPE_DOUBLE ? 12 : 1;
+  const unsigned ebits = min_bits(type);
   // One wave's LDS image must fit a workgroup's LDS beside the tables: the
   // decoder's (maxbits / 32 + 5 rows of 256 B + 16 KiB of chunk tables) takes
   // 145 KiB at CUZFP_MAX_BITS (16,384) of gfx950's 160 KiB (the launchers
@@ -800,15 +803,19 @@ int cuzfp_hip_decode(const uint64_t* d_stream, size_t stream_bytes, int type, un
   return launch_decode(p, d_stream, d_data, 0, waves_of(p.g), stream);
 }
 
-int cuzfp_hip_decode_region(const uint64_t* d_stream, size_t stream_bytes, int type,
-                            unsigned nx, unsigned ny, unsigned nz, unsigned maxbits,
-                            unsigned ox, unsigned oy, unsigned oz,
-                            unsigned ex, unsigned ey, unsigned ez,
-                            long long sx, long long sy, long long sz,
-                            void* d_out, hipStream_t stream) {
+// cuzfp_hip_decode_region (prefix_bits == maxbits) and
+// cuzfp_hip_decode_region_prefix: blocks maxbits apart, each decoded with a
+// budget of prefix_bits
+static int decode_region_impl(const uint64_t* d_stream, size_t stream_bytes, int type,
+                              unsigned nx, unsigned ny, unsigned nz, unsigned maxbits, unsigned prefix_bits,
+                              unsigned ox, unsigned oy, unsigned oz,
+                              unsigned ex, unsigned ey, unsigned ez,
+                              long long sx, long long sy, long long sz,
+                              void* d_out, hipStream_t stream) {
   Problem p;
   int rc = make_problem(type, nx, ny, nz, 0, 0, 0, maxbits, &p);
   if (rc) return rc;
+  if (prefix_bits < min_bits(type) || prefix_bits > maxbits) return CUZFP_ERROR_INVALID_ARGUMENT;
   if (!d_out || !d_stream) return CUZFP_ERROR_INVALID_ARGUMENT;
   // an unused dimension takes origin 0 and extent 0 (as ny, nz = 0)
   if (p.dims < 2 && (oy || ey)) return CUZFP_ERROR_INVALID_ARGUMENT;
@@ -828,11 +835,55 @@ int cuzfp_hip_decode_region(const uint64_t* d_stream, size_t stream_bytes, int t
                     (p.dims < 3 || !((oz | ez) & 3)) && r.sx == 1 && r.sy == (long long)ex &&
                     r.sz == (long long)ex * ey && ((uintptr_t)d_out & 15) == 0;
   switch (type) {
-    case CUZFP_TYPE_INT32: return launch_decode_region_type<int32_t>(p, r, d_stream, false, d_out, stream);
-    case CUZFP_TYPE_INT64: return launch_decode_region_type<int64_t>(p, r, d_stream, false, d_out, stream);
-    case CUZFP_TYPE_FLOAT: return launch_decode_region_type<float>(p, r, d_stream, fast, d_out, stream);
-    default: return launch_decode_region_type<double>(p, r, d_stream, fast, d_out, stream);
+    case CUZFP_TYPE_INT32: return launch_decode_region_type<int32_t>(p, r, d_stream, false, prefix_bits, d_out, stream);
+    case CUZFP_TYPE_INT64: return launch_decode_region_type<int64_t>(p, r, d_stream, false, prefix_bits, d_out, stream);
+    case CUZFP_TYPE_FLOAT: return launch_decode_region_type<float>(p, r, d_stream, fast, prefix_bits, d_out, stream);
+    default: return launch_decode_region_type<double>(p, r, d_stream, fast, prefix_bits, d_out, stream);
   }
+}
+
+int cuzfp_hip_decode_region(const uint64_t* d_stream, size_t stream_bytes, int type,
+                            unsigned nx, unsigned ny, unsigned nz, unsigned maxbits,
+                            unsigned ox, unsigned oy, unsigned oz,
+                            unsigned ex, unsigned ey, unsigned ez,
+                            long long sx, long long sy, long long sz,
+                            void* d_out, hipStream_t stream) {
+  return decode_region_impl(d_stream, stream_bytes, type, nx, ny, nz, maxbits, maxbits, ox, oy, oz, ex, ey, ez,
+                            sx, sy, sz, d_out, stream);
+}
+
+int cuzfp_hip_decode_region_prefix(const uint64_t* d_stream, size_t stream_bytes, int type,
+                                   unsigned nx, unsigned ny, unsigned nz,
+                                   unsigned maxbits, unsigned prefix_bits,
+                                   unsigned ox, unsigned oy, unsigned oz,
+                                   unsigned ex, unsigned ey, unsigned ez,
+                                   long long sx, long long sy, long long sz,
+                                   void* d_out, hipStream_t stream) {
+  return decode_region_impl(d_stream, stream_bytes, type, nx, ny, nz, maxbits, prefix_bits, ox, oy, oz,
+                            ex, ey, ez, sx, sy, sz, d_out, stream);
+}
+
+int cuzfp_hip_truncate(const uint64_t* d_src, size_t src_bytes, int type,
+                       unsigned nx, unsigned ny, unsigned nz,
+                       unsigned maxbits, unsigned new_maxbits,
+                       uint64_t* d_dst, size_t dst_capacity, size_t* out_bytes,
+                       hipStream_t stream) {
+  Problem p;
+  int rc = make_problem(type, nx, ny, nz, 0, 0, 0, maxbits, &p);
+  if (rc) return rc;
+  // no widening: zero-padded blocks are not the higher rate's stream (cuzfp_hip.h)
+  if (new_maxbits < min_bits(type) || new_maxbits > maxbits) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_src || !d_dst) return CUZFP_ERROR_INVALID_ARGUMENT;
+  const size_t need_src = stream_bytes_of(p.g);
+  const size_t need_dst = (((size_t)p.g.nblocks * new_maxbits + 63) / 64) * 8;
+  // the ranges the kernel reads and writes must be disjoint: a block of the
+  // output would otherwise overwrite source bits another lane has yet to read
+  const uintptr_t s0 = (uintptr_t)d_src, t0 = (uintptr_t)d_dst;
+  if (s0 < t0 + need_dst && t0 < s0 + need_src) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (src_bytes < need_src || dst_capacity < need_dst) return CUZFP_ERROR_BUFFER_TOO_SMALL;
+  rc = launch_truncate(d_src, d_dst, p.g.nblocks, maxbits, new_maxbits, stream);
+  if (rc == CUZFP_SUCCESS && out_bytes) *out_bytes = need_dst;
+  return rc;
 }
 
 int cuzfp_hip_encode_region(const void* d_box, int type,

@@ -88,10 +88,13 @@ template <typename Scalar>
 int launch_decode_type(const Problem& p, const uint64_t* stream, bool fast, void* data,
                        uint32_t wave0, uint32_t nwaves, hipStream_t st);
 // The sub-box decoder (region_kernels.hpp): `out` is the box's element (0, 0, 0);
-// fast: a block-aligned box into a contiguous, 16-byte aligned `out`.
+// fast: a block-aligned box into a contiguous, 16-byte aligned `out`.  Blocks
+// sit r.maxbits apart in the stream (the stride, p.g.maxbits) and each is
+// decoded with `budget` <= r.maxbits bits (cuzfp_hip_decode_region_prefix;
+// budget == r.maxbits is cuzfp_hip_decode_region).
 template <typename Scalar>
 int launch_decode_region_type(const Problem& p, const Region& r, const uint64_t* stream, bool fast,
-                              void* out, hipStream_t st);
+                              uint32_t budget, void* out, hipStream_t st);
 
 // Every block the box touches is covered: each of its elements that lies
 // inside the array lies inside the box.  Along an axis: the origin is a
@@ -108,5 +111,10 @@ inline bool region_covered(const Geometry& g, const Region& r) {
 template <typename Scalar>
 int launch_encode_region_type(const Problem& p, const Region& r, const void* box, bool covered, bool rows,
                               uint64_t* stream, hipStream_t st);
+
+// cuzfp_hip_truncate (truncate.hip, rerate.hpp): the first m bits of each of
+// the nblocks blocks of `src` (M bits apart), packed m apart into `dst`; the
+// ranges are disjoint, m <= M.
+int launch_truncate(const uint64_t* src, uint64_t* dst, uint32_t nblocks, uint32_t M, uint32_t m, hipStream_t st);
 
 }  // namespace cuzfp

@@ -2,6 +2,6 @@
 #include "region_kernels.hpp"
 
 namespace cuzfp {
-template int launch_decode_region_type<double>(const Problem&, const Region&, const uint64_t*, bool, void*,
+template int launch_decode_region_type<double>(const Problem&, const Region&, const uint64_t*, bool, uint32_t, void*,
                                               hipStream_t);
 }  // namespace cuzfp

@@ -12,6 +12,14 @@
 // apart, as the whole-array decoder's lane-owned fallback); runs are bx (and
 // bx * by) blocks apart.
 //
+// maxbits has two roles, kept apart: the stride between blocks in the stream
+// is Region::maxbits; the budget each block is decoded with -- the bits read,
+// the image's size and masks, decode_block's argument, the register path --
+// is Geometry::maxbits.  cuzfp_hip_decode_region passes the same value for
+// both; cuzfp_hip_decode_region_prefix a budget below the stride, which
+// decodes each block's prefix (zfp's coder is embedded: rerate.hpp) and reads
+// nothing of a block past it.
+//
 // Instantiated per scalar type in region_{f32,f64,i32,i64}.hip.
 #pragma once
 #include "kernels.hpp"
@@ -66,7 +74,7 @@ __device__ __forceinline__ void zfp_decode_region_body(const uint64_t* __restric
   const RegionBlock rb = region_block<DIMS>(rg, live ? r : 0u);
   uint64_t d0;
   uint32_t s0;
-  region_block_bits(rb.b, g.maxbits, d0, s0);
+  region_block_bits(rb.b, rg.maxbits, d0, s0);
   const uint32_t* base = (const uint32_t*)stream;
   uint32_t* lut = ctab;
   auto copy_tabs = [&]() {
@@ -96,9 +104,10 @@ __device__ __forceinline__ void zfp_decode_region_body(const uint64_t* __restric
     copy_tabs();
   } else {
     const uint32_t D = (g.maxbits + 31) >> 5;  // dwords per block
-    // maxbits a multiple of 128 and a 16-byte aligned stream: every block
-    // starts 16-byte aligned (s0 = 0, d0 a multiple of 4)
-    const bool vec = (g.maxbits & 127) == 0 && g.vec_io;
+    // stride and budget multiples of 128 and a 16-byte aligned stream: every
+    // block starts 16-byte aligned (s0 = 0, d0 a multiple of 4) and is read in
+    // whole 16-byte pieces
+    const bool vec = ((g.maxbits | rg.maxbits) & 127) == 0 && g.vec_io;
     constexpr uint32_t kHeld = 8;  // 16-byte pieces held in registers (maxbits <= 1024)
     uint4 held[kHeld];
     const uint4* src = (const uint4*)(base + d0);
@@ -207,8 +216,11 @@ __global__ __launch_bounds__(kLanes * WPG, (occupancy<Scalar, DIMS>::value)) voi
 // and no plane-loop priority schedule, whose thresholds were measured for
 // whole-array launches.
 template <typename Scalar, int DIMS>
-int launch_decode_region_t(const uint64_t* stream, const Geometry& g, const Region& rg, bool fast,
-                           void* out, hipStream_t st) {
+int launch_decode_region_t(const uint64_t* stream, const Geometry& g0, const Region& rg, bool fast,
+                           uint32_t budget, void* out, hipStream_t st) {
+  // the kernel's Geometry carries the budget; the stride stays in rg.maxbits
+  Geometry g = g0;
+  g.maxbits = budget;
   Geometry gg = g;
   const uint32_t nwaves = (rg.nrb + kLanes - 1) / kLanes;
   // the box as an array of its own (the fast row stores)
@@ -256,11 +268,11 @@ int launch_decode_region_t(const uint64_t* stream, const Geometry& g, const Regi
 
 template <typename Scalar>
 int launch_decode_region_type(const Problem& p, const Region& r, const uint64_t* stream, bool fast,
-                              void* out, hipStream_t st) {
+                              uint32_t budget, void* out, hipStream_t st) {
   switch (p.dims) {
-    case 1: return launch_decode_region_t<Scalar, 1>(stream, p.g, r, fast, out, st);
-    case 2: return launch_decode_region_t<Scalar, 2>(stream, p.g, r, fast, out, st);
-    default: return launch_decode_region_t<Scalar, 3>(stream, p.g, r, fast, out, st);
+    case 1: return launch_decode_region_t<Scalar, 1>(stream, p.g, r, fast, budget, out, st);
+    case 2: return launch_decode_region_t<Scalar, 2>(stream, p.g, r, fast, budget, out, st);
+    default: return launch_decode_region_t<Scalar, 3>(stream, p.g, r, fast, budget, out, st);
   }
 }
 

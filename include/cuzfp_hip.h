@@ -168,6 +168,73 @@ int cuzfp_hip_encode_region(const void* d_box, int type,
                             long long sx, long long sy, long long sz,
                             uint64_t* d_stream, size_t stream_bytes, hipStream_t stream);
 
+/* Not a reference entry point (callers test CUZFP_HIP_HAS_TRUNCATE): lower a
+ * stream's rate without decoding it.  zfp's coder is embedded: a block coded
+ * with a budget of m bits is the first m bits of the same block coded with any
+ * larger budget M.  So the stream of an array at new_maxbits is the stream at
+ * maxbits >= new_maxbits with every block cut down to its first new_maxbits
+ * bits: store once at a high rate, ship or preview at a lower one.  Unlike
+ * decoding and encoding again, this gives the low-rate stream of the ORIGINAL
+ * values, bit for bit, and moves no uncompressed data.
+ *
+ * d_src holds the stream of an nx x ny x nz array of `type` at maxbits (as for
+ * cuzfp_hip_decode).  Bits [b*m, (b+1)*m) of d_dst become bits [b*M, b*M + m)
+ * of d_src for every block b (M = maxbits, m = new_maxbits); the bits from
+ * nblocks*m up to the end of the last 64-bit word become zero, so d_dst is
+ * byte-identical to what cuzfp_hip_encode gives at new_maxbits.  Exactly
+ * cuzfp_hip_stream_bytes(type, nx, ny, nz, new_maxbits) bytes of d_dst are
+ * written -- *out_bytes (optional) receives that count -- and no byte of
+ * d_dst past them is touched.  new_maxbits == maxbits is a plain copy.
+ *
+ * There is no widening: new_maxbits > maxbits is CUZFP_ERROR_INVALID_ARGUMENT.
+ * Zero-padding each block up to a higher rate does NOT decode to the same
+ * values.  When the budget runs out inside a group scan the decoder still
+ * deposits the pending one-bit where it stands; with trailing zeros appended
+ * the scan runs on to the end of the bit plane and deposits it elsewhere.
+ * new_maxbits has maxbits' lower bound (9 float, 12 double, 1 integer).
+ *
+ * There is no in-place form either, because blocks would race: the byte
+ * ranges [d_src, + stream_bytes at maxbits) and [d_dst, + stream_bytes at
+ * new_maxbits) must not overlap (the two addresses are compared on the host;
+ * CUZFP_ERROR_INVALID_ARGUMENT, as for a null pointer).  They may be adjacent.
+ * CUZFP_ERROR_BUFFER_TOO_SMALL when src_bytes or dst_capacity is less than the
+ * respective stream.
+ *
+ * Asynchronous on `stream`: one kernel launch, no allocation, no
+ * synchronisation; it can be captured into a hipGraph.  When both rates are
+ * multiples of 64 bits (every 3D stream of cuZFP::compress) whole words move,
+ * 16 bytes a lane when both are multiples of 128 and both pointers 16-byte
+ * aligned; any other pair is assembled a 64-bit output word a lane. */
+#define CUZFP_HIP_HAS_TRUNCATE 1
+int cuzfp_hip_truncate(const uint64_t* d_src, size_t src_bytes, int type,
+                       unsigned nx, unsigned ny, unsigned nz,
+                       unsigned maxbits, unsigned new_maxbits,
+                       uint64_t* d_dst, size_t dst_capacity, size_t* out_bytes,
+                       hipStream_t stream);
+
+/* Not a reference entry point (callers test CUZFP_HIP_HAS_DECODE_PREFIX):
+ * cuzfp_hip_decode_region at a lower rate than the stream's, by the prefix
+ * property above.  The blocks of d_stream sit maxbits apart; each is decoded
+ * with a budget of prefix_bits <= maxbits.  The result is bit-identical to
+ * cuzfp_hip_decode_region at prefix_bits on the stream cuzfp_hip_truncate
+ * makes, but no intermediate stream is made and only the first prefix_bits
+ * of each of the box's blocks are read.  prefix_bits has maxbits' lower bound
+ * (9 float, 12 double, 1 integer); prefix_bits > maxbits is
+ * CUZFP_ERROR_INVALID_ARGUMENT (no widening); prefix_bits == maxbits is
+ * cuzfp_hip_decode_region.  Every other argument, the status codes and the
+ * launch (one kernel, asynchronous, graph-capturable) are
+ * cuzfp_hip_decode_region's; stream_bytes must cover the whole stream at
+ * maxbits.  A whole-array decode at a lower rate is the box (0, 0, 0) +
+ * (nx, ny, nz). */
+#define CUZFP_HIP_HAS_DECODE_PREFIX 1
+int cuzfp_hip_decode_region_prefix(const uint64_t* d_stream, size_t stream_bytes, int type,
+                                   unsigned nx, unsigned ny, unsigned nz,
+                                   unsigned maxbits, unsigned prefix_bits,
+                                   unsigned ox, unsigned oy, unsigned oz,
+                                   unsigned ex, unsigned ey, unsigned ez,
+                                   long long sx, long long sy, long long sz,
+                                   void* d_out, hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,

@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "build", "var")
 UNITS = ("inst_f32", "inst_f64", "inst_i32", "inst_i64",
          "region_f32", "region_f64", "region_i32", "region_i64",
-         "update_f32", "update_f64", "update_i32", "update_i64", "capi")
+         "update_f32", "update_f64", "update_i32", "update_i64", "truncate", "capi")
 
 
 def build(pairs):

@@ -39,7 +39,8 @@ def _stub_objs(unit):
     for u, flags in (("inst_f32", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("inst_f64", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]),
                      ("inst_i32", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("inst_i64", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]),
                      ("region_f32", []), ("region_f64", []), ("region_i32", []), ("region_i64", []),
-                     ("update_f32", []), ("update_f64", []), ("update_i32", []), ("update_i64", []), ("capi", [])):
+                     ("update_f32", []), ("update_f64", []), ("update_i32", []), ("update_i64", []), ("truncate", []),
+                     ("capi", [])):
         if u == unit:
             continue
         o = os.path.join(STUB, u + ".o")
