@@ -1097,28 +1097,6 @@ ZFP_HD void encode_plane_step(PW x, unsigned& n, Writer& wr) {
   }
 }
 
-// Planes 31 .. cmin of 32-bit half H, two at a time (an odd one left at the
-// bottom goes alone); false once the block is full.
-template <int H, typename UInt, int DIMS, typename Writer>
-ZFP_HD bool encode_half(const planes<UInt, DIMS>& P, unsigned& n, int cmin, Writer& wr) {
-  typedef typename plane_word<DIMS>::type PW;
-  int c = 31;
-  for (; c - 1 >= cmin; c -= 2) {
-    if (!any_lane(!wr.full())) return false;
-    wr.settle();
-    const int u = uniform(c);
-    if constexpr (prio_of<Writer>::value) progress_priority<CUZFP_PRIO_T2, CUZFP_PRIO_T1, CUZFP_PRIO_T0>(u);
-    encode_plane_step<DIMS>((PW)P.template get<H>(u), n, wr);
-    encode_plane_step<DIMS>((PW)P.template get<H>(u - 1), n, wr);
-  }
-  if (c >= cmin && c >= 0) {
-    if (!any_lane(!wr.full())) return false;
-    wr.settle();
-    encode_plane_step<DIMS>((PW)P.template get<H>(uniform(c)), n, wr);
-  }
-  return true;
-}
-
 // Planes 31 .. 0 of half H with compile-time plane numbers (every lane of the
 // wave codes all 32 planes while it has budget): each plane word is a fixed
 // register, so there is no VGPR-relative addressing (s_set_gpr_idx_on / off
@@ -1267,14 +1245,17 @@ ZFP_HD bool encode_pairs_1d(const planes<UInt, 1>& P, uint32_t& n10, Writer& wr)
   return true;
 }
 
+// Every plane down to 0, on every lane: the plane loops are wave-uniform.  A
+// double block whose precision() is below 64 has the planes it does not code
+// cleared beforehand (cut_planes in encode_block): a cleared plane codes as
+// zero bits, which is what the reference pads the block with.
 template <typename UInt, int DIMS, typename Writer>
-ZFP_HD void encode_planes(const planes<UInt, DIMS>& P, unsigned maxprec, Writer& wr) {
+ZFP_HD void encode_planes(const planes<UInt, DIMS>& P, Writer& wr) {
   constexpr int PREC = (int)sizeof(UInt) * 8;
   unsigned n = 0;
   if constexpr (PREC == 32) {
     // 32-bit coefficients are coded down to plane 0: precision() is 32 for
     // every f32 exponent (emax >= -149), and int32 has maxprec 32
-    (void)maxprec;
     if constexpr (DIMS == 1 && has_pair1d<Writer>::value) {
       uint32_t n10 = 0;
       encode_pairs_1d<0, 31>(P, n10, wr);
@@ -1282,19 +1263,13 @@ ZFP_HD void encode_planes(const planes<UInt, DIMS>& P, unsigned maxprec, Writer&
     }
     encode_half_fixed<0, 31>(P, n, wr);
   } else {
-    const int kmin = PREC > (int)maxprec ? PREC - (int)maxprec : 0;
-    if (!any_lane(kmin != 0)) {  // every lane codes down to plane 0 (normal doubles)
-      if constexpr (DIMS == 1 && has_pair1d<Writer>::value) {
-        uint32_t n10 = 0;
-        if (encode_pairs_1d<1, 31>(P, n10, wr)) encode_pairs_1d<0, 31>(P, n10, wr);
-        return;
-      }
-      // the priority schedule over the high half only
-      if (encode_half_fixed<1, 31>(P, n, wr)) encode_half_fixed<0, 31, false>(P, n, wr);
+    if constexpr (DIMS == 1 && has_pair1d<Writer>::value) {
+      uint32_t n10 = 0;
+      if (encode_pairs_1d<1, 31>(P, n10, wr)) encode_pairs_1d<0, 31>(P, n10, wr);
       return;
     }
-    if (!encode_half<1>(P, n, kmin > 32 ? kmin - 32 : 0, wr)) return;
-    encode_half<0>(P, n, kmin, wr);
+    // the priority schedule over the high half only
+    if (encode_half_fixed<1, 31>(P, n, wr)) encode_half_fixed<0, 31, false>(P, n, wr);
   }
 }
 
@@ -1813,7 +1788,8 @@ ZFP_HD PW decode_plane_lut(unsigned& bits, unsigned& n, Reader& rd, bool& slow) 
 
 // Plane loop: the table decoder for every lane, then, only when some lane of
 // the wave needs it, the general decoder for those lanes.  (n <= N-1 in and
-// out.)  Used for a rolled loop's trailing odd plane.
+// out.)  The plane loops call decode_plane_fast_any; this single step is what
+// the host's differential fuzz of the table decoder runs (tests/native/emulate.cpp).
 template <int DIMS, typename PW, typename Reader>
 ZFP_HD PW decode_plane_any(unsigned& n, Reader& rd) {
   constexpr unsigned N = 1u << (2 * DIMS);
@@ -1934,14 +1910,18 @@ ZFP_HD PW decode_plane_fast_any(unsigned& n, Reader& rd) {
   return x;
 }
 
-// Planes 31 .. cmin of 32-bit half H, two per loop trip, while any lane of the
+// Planes 31 .. 0 of 32-bit half H, two per loop trip, while any lane of the
 // wave has budget (a lane without deposits zeros).  Returns the highest plane
-// left unset (-1: none); those below it are unset too.
+// left unset (-1: none); those below it are unset too.  The plane counter and
+// the return value are the same on every lane: uniform() and zero_planes rely
+// on it, so no bound of this loop may depend on the lane (a lane that stops at
+// a plane of its own -- precision() below 64 -- decodes on and has those
+// planes cleared afterwards, cut_planes in decode_block).
 template <int H, typename UInt, int DIMS, typename Reader>
-ZFP_HD int decode_half(planes<UInt, DIMS>& P, unsigned& n, int cmin, Reader& rd) {
+ZFP_HD int decode_half(planes<UInt, DIMS>& P, unsigned& n, Reader& rd) {
   typedef typename plane_word<DIMS>::type PW;
   int c = 31;
-  for (; c - 1 >= cmin; c -= 2) {
+  for (; c >= 1; c -= 2) {
     if (!any_lane(rd.pos < rd.end)) return c;
     if constexpr (prio_of<Reader>::value)
       progress_priority<CUZFP_DPRIO_T2, CUZFP_DPRIO_T1, CUZFP_DPRIO_T0>(uniform(c));
@@ -1952,10 +1932,6 @@ ZFP_HD int decode_half(planes<UInt, DIMS>& P, unsigned& n, int cmin, Reader& rd)
     const int u = uniform(c);
     P.template set<H>(u, xa);
     P.template set<H>(u - 1, xb);
-  }
-  if (c >= cmin && c >= 0 && any_lane(rd.pos < rd.end)) {
-    P.template set<H>(uniform(c), decode_plane_any<DIMS, PW>(n, rd));
-    c--;
   }
   return c;
 }
@@ -2056,8 +2032,10 @@ ZFP_HD void decode_planes_1d(planes<UInt, 1>& P, uint32_t& n12, Reader& rd) {
 
 // Returns the highest plane left unset by a 32-bit coefficients' loop (-1:
 // none; every plane below it is unset too), 31 otherwise (nothing known).
+// Every lane decodes down to plane 0 while it has budget, whatever its
+// precision(): see decode_half.
 template <typename UInt, int DIMS, typename Reader>
-ZFP_HD int decode_planes(planes<UInt, DIMS>& P, unsigned budget, unsigned maxprec, Reader& rd) {
+ZFP_HD int decode_planes(planes<UInt, DIMS>& P, unsigned budget, Reader& rd) {
   constexpr int PREC = (int)sizeof(UInt) * 8;
   unsigned n = 0;
   rd.end = rd.pos + budget;  // the reader never passes it
@@ -2065,7 +2043,6 @@ ZFP_HD int decode_planes(planes<UInt, DIMS>& P, unsigned budget, unsigned maxpre
   if constexpr (PREC == 32) {
     // every plane down to 0 (see encode_planes); the early exits of the
     // unrolled loop zero what they leave
-    (void)maxprec;
     if constexpr (DIMS == 1 && has_dec1d<Reader>::value) {
       uint32_t n12 = 0;
       decode_planes_1d<0, 31>(P, n12, rd);
@@ -2073,25 +2050,37 @@ ZFP_HD int decode_planes(planes<UInt, DIMS>& P, unsigned budget, unsigned maxpre
     }
     return decode_half_fixed<0, 31>(P, n, rd);
   } else {
-    const int kmin = PREC > (int)maxprec ? PREC - (int)maxprec : 0;
     if constexpr (DIMS == 1 && has_dec1d<Reader>::value) {
-      if (!any_lane(kmin != 0)) {  // every lane decodes down to plane 0
-        uint32_t n12 = 0;
-        decode_planes_1d<1, 31>(P, n12, rd);
-        decode_planes_1d<0, 31>(P, n12, rd);
-        return 31;
-      }
+      uint32_t n12 = 0;
+      decode_planes_1d<1, 31>(P, n12, rd);
+      decode_planes_1d<0, 31>(P, n12, rd);
+      return 31;
     }
     // (64-bit values keep the rolled loop: unrolled, the f64 decoder measured
     // 61.8 -> 71.2 us at 256^3 rate 16 and took minutes to compile)
-    zero_planes<1>(P, decode_half<1>(P, n, kmin > 32 ? kmin - 32 : 0, rd));
-    if (kmin >= 32) {
-      zero_planes<0>(P, 31);
-      return 31;
-    }
-    zero_planes<0>(P, decode_half<0>(P, n, kmin, rd));
+    zero_planes<1>(P, decode_half<1>(P, n, rd));
+    zero_planes<0>(P, decode_half<0>(P, n, rd));
   }
   return 31;
+}
+
+// The planes below 64 - maxprec of a double block are not coded (precision()
+// is below 64 for exponents near the denormal range: codec*.c precision()).
+// The plane loops run down to plane 0 on every lane all the same -- their
+// bounds are wave-uniform -- and the lanes concerned have those planes cleared
+// here instead: before the encoder's transpose, after the decoder's.  v holds
+// coefficients whose planes are v ^ NB (the encoder's q + NB, the decoder's
+// store<true>() output), so a cleared plane is NB's bit.  A wave-uniform test
+// first: normal doubles never come here.
+template <typename UInt, int N>
+ZFP_HD void cut_planes(UInt* v, unsigned maxprec) {
+  constexpr unsigned PREC = (unsigned)sizeof(UInt) * 8;
+  if (__builtin_expect(any_lane(maxprec != PREC), 0)) {
+    const UInt m = (UInt)lowmask(PREC - maxprec);
+    constexpr UInt NB = nbmask<UInt>::value;
+#pragma unroll
+    for (int i = 0; i < N; i++) v[i] = (v[i] & ~m) | (NB & m);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2276,6 +2265,7 @@ ZFP_HD void encode_block(const Scalar* f, unsigned maxbits, Writer& wr) {
     const unsigned e = maxprec ? (unsigned)(emax + T::ebias) : 0u;
     // all-zero block: a single 0 bit, then padding (encode.c:206-215)
     bool zero = !e;
+    if (zero) maxprec = T::prec;  // nothing to cut (cut_planes), whatever precision(emax) says
     if constexpr (zero_inline_of<Writer>::value) {
       // ... coded inline: marked full (its bits all go to the discarded
       // slack, its column stays zero), quantised with a zero scale (q = 0);
@@ -2313,6 +2303,7 @@ ZFP_HD void encode_block(const Scalar* f, unsigned maxbits, Writer& wr) {
   UInt u[N];
   constexpr UInt NB = nbmask<UInt>::value;
   permute_fwd_add<DIMS>(q, u, NB, make_seq<N>());  // "^ NB" in P.load<true>
+  if constexpr (sizeof(UInt) == 8 && !T::is_int) cut_planes<UInt, N>(u, maxprec);
   ZFP_STAMP(2);
 #if defined(CUZFP_PROBE) && (CUZFP_PROBE == 1 || CUZFP_PROBE == 2)
   // timing probes (tools/probe.py; never built into the product library):
@@ -2348,30 +2339,22 @@ ZFP_HD void encode_block(const Scalar* f, unsigned maxbits, Writer& wr) {
     // 3D 64-bit blocks: the low half's tiles transposed a 16-plane part at a
     // time, each only if some lane of the wave still has budget
     // (planes::load_split), in the lane-interleaved image's kernels (with the
-    // bit-packed image the kernel spills in its main path).  One consumer of u: a second layout of u for a
-    // separate rolled path made the kernel spill in its main path.
+    // bit-packed image the kernel spills in its main path).
     planes<UInt, DIMS> PS;
     PS.template load_split<true>(u);
     ZFP_STAMP(3);
     unsigned n = 0;
-    if (__builtin_expect(!any_lane(maxprec != T::prec), 1)) {  // normal doubles, int64: down to plane 0
-      if (encode_half_fixed<1, 31>(PS, n, wr)) {
-        PS.template lo_part<true, true>();
-        if (encode_half_fixed<0, 31, false, 16>(PS, n, wr)) {
-          PS.template lo_part<true, false>();
-          encode_half_fixed<0, 15, false>(PS, n, wr);
-        }
-      }
-    } else {  // some lane stops above plane 0: encode_planes' rolled loops
+    if (encode_half_fixed<1, 31>(PS, n, wr)) {
       PS.template lo_part<true, true>();
-      PS.template lo_part<true, false>();
-      const int kmin = 64 - (int)maxprec;
-      if (encode_half<1>(PS, n, kmin > 32 ? kmin - 32 : 0, wr)) encode_half<0>(PS, n, kmin, wr);
+      if (encode_half_fixed<0, 31, false, 16>(PS, n, wr)) {
+        PS.template lo_part<true, false>();
+        encode_half_fixed<0, 15, false>(PS, n, wr);
+      }
     }
   } else {
     P.template load<true>(u);
     ZFP_STAMP(3);
-    encode_planes<UInt, DIMS>(P, maxprec, wr);
+    encode_planes<UInt, DIMS>(P, wr);
   }
   ZFP_STAMP(4);
 #endif
@@ -2405,7 +2388,8 @@ ZFP_HD bool decode_block(Scalar* f, unsigned maxbits, Reader& rd) {
     emax = (int)((head >> 1) & lowmask(T::ebits)) - T::ebias;
     const auto start = rd.pos;
     rd.skip(T::ebits + 1);
-    maxprec = precision<DIMS>(emax, T::prec);
+    // (a zero block's header bits are arbitrary: nothing to cut, cut_planes)
+    maxprec = coded ? precision<DIMS>(emax, T::prec) : (unsigned)T::prec;
     budget = coded ? maxbits - (T::ebits + 1) : 0u;
     // (the plane steps take the stream as zeros past the budget's end, which
     // a zero block's bits need not be: its reads start at the block's end,
@@ -2432,7 +2416,7 @@ ZFP_HD bool decode_block(Scalar* f, unsigned maxbits, Reader& rd) {
   P.store(u);
 #else
   planes<UInt, DIMS> P;
-  const int unset = decode_planes<UInt, DIMS>(P, budget, maxprec, rd);
+  const int unset = decode_planes<UInt, DIMS>(P, budget, rd);
   (void)unset;
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(CUZFP_NO_PRIO) && CUZFP_DPRIO_AFTER >= 0
   if constexpr (prio_of<Reader>::value) __builtin_amdgcn_s_setprio(CUZFP_DPRIO_AFTER);  // see progress_priority
@@ -2453,6 +2437,7 @@ ZFP_HD bool decode_block(Scalar* f, unsigned maxbits, Reader& rd) {
     ZFP_STAMP(2);
   } else {
     P.template store<true>(u);  // u ^ NB
+    if constexpr (sizeof(UInt) == 8 && !T::is_int) cut_planes<UInt, N>(u, maxprec);
     ZFP_STAMP(2);
     permute_inv_sub<DIMS>(u, q, NB, make_seq<N>());  // (u ^ NB) - NB
   }

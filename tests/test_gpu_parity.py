@@ -684,8 +684,8 @@ def test_split_transpose_64bit(cuda, restatement, dtype):
     while some lane of the wave has budget (zfp_block.hpp, planes::load_split):
     rates that stop waves above plane 32, between 32 and 16 and below 16, in
     aligned (lane-interleaved image) arrays, with waves mixing blocks of every
-    magnitude and, for doubles, tiny-exponent blocks (maxprec < 64: the rolled
-    path after the split transpose) beside normal ones."""
+    magnitude and, for doubles, tiny-exponent blocks (maxprec < 64: cut_planes
+    before the split transpose) beside normal ones."""
     rng = np.random.default_rng(641)
     shape = (8, 16, 256)  # whole waves of 64 blocks along x
     if dtype == np.float64:

@@ -2,7 +2,10 @@
 cuzfp_hip_decode_region).
 
 The expected value of every GPU case is the box cut out of the CPU oracle's
-decode of the whole array, compared bit for bit; the stream is the oracle's.
+decode of the whole array, compared bit for bit.  The stream is the oracle's
+of a smooth field, of the block zoo (tests/block_zoo.py: zero blocks beside
+coded ones, a wave of zero blocks, NaN, inf, denormal and huge blocks) or
+arbitrary bits that no encoder wrote.
 The argument checks and the host program over csrc/region.hpp need no GPU.
 """
 import ctypes
@@ -13,6 +16,7 @@ import zlib
 import numpy as np
 import pytest
 
+import block_zoo as bz
 import cuzfp_amd as cz
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,9 +64,10 @@ def _same_bytes(got, want):
     return got.shape == want.shape and np.array_equal(got.view(np.uint8), want.view(np.uint8))
 
 
-def _check_boxes(cuda, restatement, shape, dtype, mb, boxes):
+def _check_boxes(cuda, restatement, shape, dtype, mb, boxes, reference=None):
+    """`reference`: the (array, stream, oracle decode) to use instead of _reference's."""
     import torch
-    _, ref, want = _reference(restatement, shape, dtype, mb)
+    _, ref, want = reference or _reference(restatement, shape, dtype, mb)
     words = _words(ref, cuda)
     td = _torch_dtype(dtype)
     for origin, extent in boxes:
@@ -110,13 +115,79 @@ BOXES1 = [((0,), (1203,)), ((7,), (1,)), ((3,), (1000,)), ((8,), (640,)), ((1199
 
 @gpu
 @pytest.mark.parametrize("mb", [17, 32, 33, 64, 128, 200])
-@pytest.mark.parametrize("dtype", [np.float32, np.int32])
+@pytest.mark.parametrize("dtype", [np.float32, np.int32, np.float64, np.int64])
 @pytest.mark.parametrize("dims", [1, 2])
 def test_region_1d_2d(cuda, restatement, dims, dtype, mb):
     """maxbits <= 64: the register reader with a per-lane base (17: several
     blocks a dword); above: the LDS image."""
     shape, boxes = (SHAPE1, BOXES1) if dims == 1 else (SHAPE2, BOXES2)
     _check_boxes(cuda, restatement, shape, dtype, mb, boxes)
+
+
+# The zoo: 64 blocks along x, so a box of whole x-rows of blocks is a box of
+# whole waves.  Wave 0 holds zero blocks only, wave 3 one zero block at lane
+# ZERO_LANE (x = 4 * 17 = 68) among dense noise.
+ZOO_BOXES = {
+    1: [((0,), (1024,)),            # the whole array
+        ((0,), (256,)),             # the zero wave alone
+        ((256,), (512,)),           # whole waves 1 and 2
+        ((515,), (400,)),           # unaligned, through waves 2 and 3
+        ((768 + 68,), (4,))],       # the zero block of wave 3
+    2: [((0, 0), (16, 256)), ((0, 0), (4, 256)), ((4, 0), (8, 256)), ((9, 5), (6, 200)), ((12, 68), (4, 4))],
+    3: [((0, 0, 0), (4, 16, 256)), ((0, 0, 0), (4, 4, 256)), ((0, 4, 0), (4, 8, 256)), ((1, 9, 5), (2, 6, 200)),
+        ((0, 12, 68), (4, 4, 4))],
+}
+_ZOO_REF = {}
+
+
+def _zoo_reference(restatement, dims, dtype, mb):
+    key = (dims, np.dtype(dtype).str, mb)
+    if key not in _ZOO_REF:
+        a, names = bz.zoo(dims, dtype)
+        assert names[0] == names[63] == names[192 + bz.ZERO_LANE] == "zero"
+        ref = restatement.compress(a, mb)
+        want = restatement.decompress(ref, a.shape, dtype, mb)
+        for v in (ref, want):
+            v.setflags(write=False)
+        _ZOO_REF[key] = (a, ref, want)
+    return _ZOO_REF[key]
+
+
+def _zoo_cases():
+    for dims in (1, 2, 3):
+        for dtype in bz.DTYPES:
+            for mb in ((33,) if dims < 3 else ()) + (64, 100, 512):
+                yield pytest.param(dims, dtype, mb, id=f"{dims}d-{np.dtype(dtype).name}-{mb}")
+
+
+@gpu
+@pytest.mark.parametrize("dims,dtype,mb", list(_zoo_cases()))
+def test_region_zoo(cuda, restatement, dims, dtype, mb):
+    """decode_block returning false (a wave of zero blocks) inside the region
+    kernels, a zero block beside coded ones, and blocks of NaN, inf, -0.0,
+    denormal and huge values; 33: the register reader."""
+    ref = _zoo_reference(restatement, dims, dtype, mb)
+    # the premise: the zero wave decodes to +0, the box that holds it alone too
+    origin, extent = ZOO_BOXES[dims][1]
+    assert not ref[2][_box(origin, extent)].view(np.uint8).any()
+    _check_boxes(cuda, restatement, bz.SHAPES[dims], dtype, mb, ZOO_BOXES[dims], reference=ref)
+
+
+@gpu
+@pytest.mark.parametrize("density", [0.5, 0.05, 0.95])
+@pytest.mark.parametrize("dtype", bz.DTYPES, ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("dims", [1, 2, 3])
+def test_region_random_streams(cuda, restatement, dims, dtype, density):
+    """Streams that are not encoder output: arbitrary bits through the region
+    copy-in (the funnel shift from a per-lane bit offset, the last-dword mask,
+    the slack rows) into LdsReader<false> and RegReader<false, false>, whose
+    budget-cut and past-the-end cases encoder output rarely reaches."""
+    shape, boxes = {1: (SHAPE1, BOXES1), 2: (SHAPE2, BOXES2), 3: (SHAPE3, BOXES3)}[dims]
+    rng = np.random.default_rng(zlib.crc32(f"random/{dims}/{np.dtype(dtype).str}/{density}".encode()))
+    for mb in ((17, 33, 64, 200) if dims < 3 else (100, 512)):
+        s = bz.random_stream(rng, bz.nblocks(shape), mb, density)
+        want = restatement.decompress(s, shape, dtype, mb)
+        _check_boxes(cuda, restatement, shape, dtype, mb, boxes, reference=(None, s, want))
 
 
 @gpu

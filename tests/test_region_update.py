@@ -7,7 +7,9 @@ call, synchronises and compares the whole stream's bytes with
     splice(old, R.compress(paste(R.decompress(old), box, new)), blocks_of(box))
 
 computed on the CPU (R: oracle.restatement; splice copies the bit ranges of
-the box's blocks from the second stream into the first).  The argument checks
+the box's blocks from the second stream into the first).  The old stream is
+the oracle's of a smooth field, of the block zoo (tests/block_zoo.py), or
+arbitrary bits that no encoder wrote; the formula is the same.  The argument checks
 and the host program over csrc/region.hpp need no GPU.
 """
 import ctypes
@@ -18,6 +20,7 @@ import zlib
 import numpy as np
 import pytest
 
+import block_zoo as bz
 import cuzfp_amd as cz
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -132,8 +135,10 @@ def _update(cuda, old, shape, dtype, mb, origin, box_values, base_offset=0):
     return words.cpu().numpy().view(np.uint64)
 
 
-def _check_boxes(cuda, restatement, shape, dtype, mb, boxes, base_offset=0):
-    old, dec, new = _reference(restatement, shape, dtype, mb)
+def _check_boxes(cuda, restatement, shape, dtype, mb, boxes, base_offset=0, reference=None):
+    """`reference`: the (old stream, its oracle decode, new values) to use
+    instead of _reference's."""
+    old, dec, new = reference or _reference(restatement, shape, dtype, mb)
     for origin, extent in boxes:
         vals = new[_box(origin, extent)]
         want = _expect(restatement, old, dec, shape, dtype, mb, origin, vals)
@@ -193,13 +198,81 @@ BOXES1 = [((0,), (1203,)), ((7,), (1,)), ((3,), (1000,)), ((8,), (640,)), ((1199
 
 @gpu
 @pytest.mark.parametrize("mb", [17, 32, 33, 64, 128, 200])
-@pytest.mark.parametrize("dtype", [np.float32, np.int32])
+@pytest.mark.parametrize("dtype", [np.float32, np.int32, np.float64, np.int64])
 @pytest.mark.parametrize("dims", [1, 2])
 def test_update_1d_2d(cuda, restatement, dims, dtype, mb):
     """17: several blocks a dword, every store an atomic; 32, 64: no atomics;
     33: a one-bit carry; 128: 16-byte stores; 200: head, whole dwords and tail."""
     shape, boxes = (SHAPE1, BOXES1) if dims == 1 else (SHAPE2, BOXES2)
     _check_boxes(cuda, restatement, shape, dtype, mb, boxes)
+
+
+# The zoo (64 blocks along x: a box of whole x-rows of blocks is a box of whole
+# waves; wave 0 holds zero blocks only).
+ZOO_BOXES = {
+    1: [((256,), (512,)),           # block-aligned, waves 1 and 2: covered
+        ((515,), (400,)),           # unaligned, through waves 2 and 3: merge
+        ((0,), (256,)),             # the zero wave alone, covered
+        ((3,), (250,))],            # inside the zero wave, unaligned: merge over decoded zero blocks
+    2: [((4, 64), (8, 128)), ((9, 5), (6, 200)), ((0, 0), (4, 256)), ((1, 3), (2, 250))],
+    3: [((0, 4, 64), (4, 8, 128)), ((1, 9, 5), (2, 6, 200)), ((0, 0, 0), (4, 4, 256)), ((1, 1, 3), (2, 2, 250))],
+}
+_ZOO_REF = {}
+
+
+def _zoo_reference(restatement, dims, dtype, mb, rotate):
+    key = (dims, np.dtype(dtype).str, mb, rotate)
+    if key not in _ZOO_REF:
+        a, _ = bz.zoo(dims, dtype)
+        new, _ = bz.zoo(dims, dtype, rotate=rotate)
+        old = restatement.compress(a, mb)
+        dec = restatement.decompress(old, a.shape, dtype, mb)
+        for v in (old, dec):
+            v.setflags(write=False)
+        _ZOO_REF[key] = (old, dec, new)
+    return _ZOO_REF[key]
+
+
+def _zoo_cases():
+    for dims in (1, 2, 3):
+        for dtype in (np.float32, np.float64):
+            for mb in ((33,) if dims < 3 else ()) + (64, 100, 512):
+                yield pytest.param(dims, dtype, mb, id=f"{dims}d-{np.dtype(dtype).name}-{mb}")
+
+
+@gpu
+@pytest.mark.parametrize("rotate", [1, 2])
+@pytest.mark.parametrize("dims,dtype,mb", list(_zoo_cases()))
+def test_update_zoo(cuda, restatement, dims, dtype, mb, rotate):
+    """The old stream is the zoo's, the new values a zoo with its recipes moved
+    `rotate` waves up: 1 puts noise over the zero wave and every class (zeros,
+    NaN, inf) over coded noise blocks; 2 puts every class over the zero wave --
+    the merge then decodes all zeros (decode_block returns false) and the box
+    brings NaN -- and zeros over the every-class wave.  Floats only: the paste
+    of a decoded integer zoo can leave the range in which the oracle's integer
+    transform does not overflow; integer types keep the recipe of _values."""
+    _check_boxes(cuda, restatement, bz.SHAPES[dims], dtype, mb, ZOO_BOXES[dims],
+                 reference=_zoo_reference(restatement, dims, dtype, mb, rotate))
+
+
+@gpu
+@pytest.mark.parametrize("density", [0.5, 0.05, 0.95])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("dims", [1, 2, 3])
+def test_update_random_old_stream(cuda, restatement, dims, dtype, density):
+    """An old stream of arbitrary bits, which no encoder wrote: the merge
+    decodes it (up to 60 % of the values +-inf at density 0.95, never NaN),
+    pastes and re-encodes; the oracle does the same and is repeatable on it.
+    float32 and float64 only: arbitrary decoded integers overflow the oracle's
+    integer transform (see _values), so this one case has no integer form."""
+    shape, boxes = {1: (SHAPE1, BOXES1), 2: (SHAPE2, BOXES2), 3: (SHAPE3, BOXES3)}[dims]
+    rng = np.random.default_rng(zlib.crc32(f"random/{dims}/{np.dtype(dtype).str}/{density}".encode()))
+    for mb in ((33, 200) if dims < 3 else (100,)):
+        old = bz.random_stream(rng, bz.nblocks(shape), mb, density)
+        dec = restatement.decompress(old, shape, dtype, mb)
+        assert not np.isnan(dec).any()
+        new = _values(rng, shape, dtype)
+        _check_boxes(cuda, restatement, shape, dtype, mb, boxes, reference=(old, dec, new))
 
 
 @gpu

@@ -12,6 +12,10 @@ oracle.restatement) -- nothing is recomputed, there are no tolerances:
 
 test_prefix_property_golden checks the property itself on the reference's own
 streams (tests/golden/streams.npz) with a numpy bit model, without the library.
+test_prefix_property_zoo checks it on the block zoo (tests/block_zoo.py), whose
+streams the zoo cases here decode.  For a stream of arbitrary bits, which no
+encoder wrote, the expectations are the definition itself (_cpu_truncate) and
+the oracle's decode of the stream so truncated.
 Every GPU case makes a fresh device copy of the source stream, one call,
 synchronises and compares whole buffers.
 """
@@ -24,6 +28,7 @@ import zlib
 import numpy as np
 import pytest
 
+import block_zoo as bz
 import cuzfp_amd as cz
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,11 +64,12 @@ def _array(shape, dtype):
     return _ARRAYS[key]
 
 
-def _stream(restatement, shape, dtype, mb):
-    """The oracle's stream of _array(shape, dtype) at mb: computed once, read only."""
-    key = (shape, np.dtype(dtype).str, mb)
+def _stream(restatement, shape, dtype, mb, zoo=False):
+    """The oracle's stream of _array(shape, dtype), or of the block zoo of that
+    shape, at mb: computed once, read only."""
+    key = (shape, np.dtype(dtype).str, mb, zoo)
     if key not in _STREAMS:
-        s = restatement.compress(_array(shape, dtype), mb)
+        s = restatement.compress(bz.zoo(len(shape), dtype, shape)[0] if zoo else _array(shape, dtype), mb)
         s.setflags(write=False)
         _STREAMS[key] = s
     return _STREAMS[key]
@@ -293,11 +299,18 @@ SHAPE1 = (1203,)
 BOXES1 = [((3,), (1000,)), ((8,), (640,)), ((1199,), (4,))]
 
 
-def _check_prefix(cuda, restatement, shape, dtype, M, m, boxes):
+def _check_prefix(cuda, restatement, shape, dtype, M, m, boxes, zoo=False, source=None):
+    """`source`: a stream at M to decode instead of the oracle's; the expected
+    value is then the oracle's decode of its CPU truncation to m."""
     import torch
     td = _torch_dtype(dtype)
-    want = restatement.decompress(_stream(restatement, shape, dtype, m), shape, dtype, m)
-    words = _words(_stream(restatement, shape, dtype, M), cuda)
+    if source is None:
+        source = _stream(restatement, shape, dtype, M, zoo)
+        lower = _stream(restatement, shape, dtype, m, zoo)
+    else:
+        lower = _cpu_truncate(source, _nblocks(shape), M, m)
+    want = restatement.decompress(lower, shape, dtype, m)
+    words = _words(source, cuda)
     for origin, extent in boxes:
         got = cz.decode_region(words, shape, td, M, origin, extent, prefix_bits=m)
         torch.cuda.synchronize()
@@ -321,7 +334,7 @@ def test_prefix_decode_3d(cuda, restatement, dtype, M, m):
 
 @gpu
 @pytest.mark.parametrize("M,m", [(128, 64), (100, 33), (64, 17), (200, 100)])
-@pytest.mark.parametrize("dtype", [np.float32, np.int32], ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("dtype", [np.float32, np.int32, np.float64, np.int64], ids=lambda d: np.dtype(d).name)
 @pytest.mark.parametrize("dims", [1, 2])
 def test_prefix_decode_1d_2d(cuda, restatement, dims, dtype, M, m):
     """(128, 64), (100, 33): the register path (budget <= 64) under a stride
@@ -329,6 +342,57 @@ def test_prefix_decode_1d_2d(cuda, restatement, dims, dtype, M, m):
     100): the LDS image."""
     shape, boxes = (SHAPE1, BOXES1) if dims == 1 else (SHAPE2, BOXES2)
     _check_prefix(cuda, restatement, shape, dtype, M, m, boxes)
+
+
+# The zoo (64 blocks along x: a box of whole x-rows of blocks is a box of whole
+# waves): the whole array, the zero wave alone, whole waves 1 and 2, an
+# unaligned box through waves 2 and 3, the zero block of wave 3.
+ZOO_PAIRS = [(512, 100), (100, 33), (128, 64)]
+ZOO_BOXES = {
+    1: [((0,), (1024,)), ((0,), (256,)), ((256,), (512,)), ((515,), (400,)), ((768 + 68,), (4,))],
+    2: [((0, 0), (16, 256)), ((0, 0), (4, 256)), ((4, 0), (8, 256)), ((9, 5), (6, 200)), ((12, 68), (4, 4))],
+    3: [((0, 0, 0), (4, 16, 256)), ((0, 0, 0), (4, 4, 256)), ((0, 4, 0), (4, 8, 256)), ((1, 9, 5), (2, 6, 200)),
+        ((0, 12, 68), (4, 4, 4))],
+}
+
+
+@gpu
+@pytest.mark.parametrize("M,m", ZOO_PAIRS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("dims", [1, 2, 3])
+def test_prefix_decode_and_truncate_zoo(cuda, restatement, dims, dtype, M, m):
+    """Zero blocks beside coded ones, a wave of zero blocks, NaN, inf, -0.0,
+    denormal and huge blocks, decoded at a lower rate than the stream's
+    (test_prefix_property_zoo holds the property), and truncated to it."""
+    import torch
+    shape = bz.SHAPES[dims]
+    _check_prefix(cuda, restatement, shape, dtype, M, m, ZOO_BOXES[dims], zoo=True)
+    out = cz.truncate(_words(_stream(restatement, shape, dtype, M, True), cuda), shape, dtype, M, m)
+    torch.cuda.synchronize()
+    assert _same_bytes(out.cpu().numpy(), _stream(restatement, shape, dtype, m, True)), (M, m)
+
+
+RANDOM_PAIRS = {1: [(128, 64), (100, 33), (64, 17), (200, 100)], 2: [(128, 64), (100, 33), (64, 17), (200, 100)],
+                3: [(1280, 100), (512, 256), (100, 33)]}
+
+
+@gpu
+@pytest.mark.parametrize("density", [0.5, 0.05, 0.95])
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("dims", [1, 2, 3])
+def test_prefix_decode_and_truncate_random_streams(cuda, restatement, dims, dtype, density):
+    """Streams that are not encoder output, on the shapes and boxes above:
+    truncate against its definition (_cpu_truncate, no oracle), prefix decode
+    against the oracle's decode of the stream so truncated."""
+    import torch
+    shape, boxes = {1: (SHAPE1, BOXES1), 2: (SHAPE2, BOXES2), 3: (SHAPE3, BOXES3)}[dims]
+    rng = np.random.default_rng(zlib.crc32(f"random/{dims}/{np.dtype(dtype).str}/{density}".encode()))
+    for M, m in RANDOM_PAIRS[dims]:
+        s = bz.random_stream(rng, _nblocks(shape), M, density)
+        out = cz.truncate(_words(s, cuda), shape, dtype, M, m)
+        torch.cuda.synchronize()
+        assert _same_bytes(out.cpu().numpy(), _cpu_truncate(s, _nblocks(shape), M, m)), (M, m)
+        _check_prefix(cuda, restatement, shape, dtype, M, m, boxes, source=s)
 
 
 @gpu
@@ -477,3 +541,16 @@ def test_prefix_property_golden():
     assert len(pairs) == 22
     for name, shape, dtype, hi, M, lo, m in pairs:
         assert _same_bytes(_cpu_truncate(hi, _nblocks(shape), M, m), lo), name
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("dims", [1, 2, 3])
+def test_prefix_property_zoo(restatement, dims, dtype):
+    """The same property on the block zoo, for the pairs its GPU cases use:
+    _cpu_truncate(R.compress(zoo, M), M -> m) == R.compress(zoo, m), zero, NaN,
+    inf, denormal and huge blocks included."""
+    shape = bz.SHAPES[dims]
+    a, _ = bz.zoo(dims, dtype)
+    for M, m in ZOO_PAIRS:
+        hi, lo = restatement.compress(a, M), restatement.compress(a, m)
+        assert _same_bytes(_cpu_truncate(hi, _nblocks(shape), M, m), lo), (M, m)
