@@ -21,6 +21,7 @@ __all__ = [
     "TYPE_INT32", "TYPE_INT64", "TYPE_FLOAT", "TYPE_DOUBLE", "CodecError",
     "library", "library_path", "rate_to_maxbits", "stream_bytes", "maximum_size",
     "encode", "decode", "decode_region", "encode_region", "truncate", "compress_host", "decompress_host", "type_code",
+    "encode_variable", "decode_variable", "accuracy_to_minexp", "variable_maximum_size",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -85,6 +86,16 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_truncate.argtypes = [vp, sz, i, u, u, u, u, u, vp, sz, ctypes.POINTER(sz), vp]
     lib.cuzfp_hip_encode_region.restype = i
     lib.cuzfp_hip_encode_region.argtypes = [vp, i, u, u, u, u, u, u, u, u, u, u, ll, ll, ll, vp, sz, vp]
+    lib.cuzfp_hip_accuracy_to_minexp.restype = i
+    lib.cuzfp_hip_accuracy_to_minexp.argtypes = [ctypes.c_double]
+    lib.cuzfp_hip_variable_maximum_size.restype = sz
+    lib.cuzfp_hip_variable_maximum_size.argtypes = [i, u, u, u, u]
+    lib.cuzfp_hip_variable_workspace_bytes.restype = sz
+    lib.cuzfp_hip_variable_workspace_bytes.argtypes = [i, u, u, u]
+    lib.cuzfp_hip_encode_variable.restype = i
+    lib.cuzfp_hip_encode_variable.argtypes = [vp, i, u, u, u, ll, ll, ll, u, i, vp, sz, vp, vp, vp, sz, vp]
+    lib.cuzfp_hip_decode_variable.restype = i
+    lib.cuzfp_hip_decode_variable.argtypes = [vp, sz, vp, i, u, u, u, ll, ll, ll, vp, vp, sz, vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -362,6 +373,133 @@ def encode_region(x, words, shape, maxbits: int, origin, stream=None):
                                            _stream_handle(stream))
     _check("encode_region", rc)
     return words
+
+
+def accuracy_to_minexp(tolerance: float) -> int:
+    """minexp of fixed-accuracy mode at `tolerance` (zfp_stream_set_accuracy:
+    floor(log2 tolerance); -1074 for a tolerance <= 0)."""
+    return int(library().cuzfp_hip_accuracy_to_minexp(float(tolerance)))
+
+
+def variable_maximum_size(shape, dtype, maxprec: int) -> int:
+    """Worst-case stream bytes of a variable-rate mode with `maxprec` planes a
+    block (the precision of fixed-precision mode; the type's 32 / 64 for fixed
+    accuracy): zfp_stream_maximum_size, header allowance included."""
+    nx, ny, nz = _extents(shape)
+    t = type_code(dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError("variable_maximum_size", 2)
+    n = library().cuzfp_hip_variable_maximum_size(t, nx, ny, nz, int(maxprec))
+    if n == 0:
+        raise CodecError("variable_maximum_size", 1)
+    return int(n)
+
+
+def _variable_workspace(t, nx, ny, nz, device, stream, where):
+    """The scratch of the variable-rate calls, allocated on the launch stream."""
+    import torch
+    n = library().cuzfp_hip_variable_workspace_bytes(t, nx, ny, nz)
+    if n == 0:
+        raise CodecError(where, 2 if t in (TYPE_INT32, TYPE_INT64) else 1)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device)):
+        return torch.empty((n + 7) // 8, dtype=torch.int64, device=device), n
+
+
+def encode_variable(x, precision=None, tolerance=None, out=None, stream=None):
+    """Compress a CUDA float tensor in one of zfp's variable-rate modes; returns
+    ``(words, lengths, nbits)``.
+
+    Exactly one of `precision` (fixed precision: that many bit planes a block,
+    1 .. 32 for float32, 1 .. 64 for float64) and `tolerance` (fixed accuracy:
+    no value off by more than `tolerance`, as far as the type's precision
+    allows; 0 codes every plane above the smallest exponent) must be given.
+
+    The stream is byte-identical to CPU zfp 0.5.0's ``zfp_compress`` after
+    ``zfp_stream_set_precision`` / ``zfp_stream_set_accuracy`` (no header).
+    `words` is a view of the stream's ceil(nbits / 64) 64-bit words in `out`
+    (allocated at the worst-case size, `variable_maximum_size`, when None; a
+    shorter `out` is never written past its end, but then holds no valid
+    stream if nbits exceeds it -- check nbits).  `lengths` is an int16 tensor
+    holding the raw uint16 bit length of every block in raster order: the
+    index `decode_variable` needs.  `nbits` is the stream's length in bits.
+
+    The launches are asynchronous on `stream` (default: torch's current), but
+    the bit count depends on the data: this function synchronises once with
+    that stream to read it back."""
+    import torch
+    if (precision is None) == (tolerance is None):
+        raise ValueError("encode_variable: give exactly one of precision and tolerance")
+    if not x.is_cuda:
+        raise ValueError("encode_variable: expects a device tensor")
+    t = type_code(x.dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError("encode_variable", 2)
+    x = _materialise(x, stream)
+    type_prec = 32 if t == TYPE_FLOAT else 64
+    if precision is not None:
+        maxprec, minexp = int(precision), -1074
+    else:
+        maxprec, minexp = type_prec, accuracy_to_minexp(tolerance)
+    if not 1 <= maxprec <= type_prec:
+        raise CodecError("encode_variable", 1)
+    nx, ny, nz = _extents(x.shape)
+    nblocks = 1
+    for s in x.shape:
+        nblocks *= (int(s) + 3) // 4
+    s = stream if stream is not None else torch.cuda.current_stream(x.device)
+    ws, ws_bytes = _variable_workspace(t, nx, ny, nz, x.device, stream, "encode_variable")
+    with torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty(variable_maximum_size(x.shape, x.dtype, maxprec) // 8, dtype=torch.int64,
+                              device=x.device)
+        lengths = torch.empty(nblocks, dtype=torch.int16, device=x.device)
+        total = torch.empty(1, dtype=torch.int64, device=x.device)
+    if not out.is_cuda or not out.is_contiguous() or out.element_size() != 8:
+        raise ValueError("encode_variable: out must be a contiguous device tensor of 64-bit words")
+    sx, sy, sz = _strides(x)
+    rc = library().cuzfp_hip_encode_variable(x.data_ptr(), t, nx, ny, nz, sx, sy, sz, maxprec, minexp,
+                                             out.data_ptr(), out.numel() * 8, lengths.data_ptr(),
+                                             total.data_ptr(), ws.data_ptr(), ws_bytes, _stream_handle(stream))
+    _check("encode_variable", rc)
+    with torch.cuda.stream(s):
+        nbits = int(total.item())  # the one synchronisation: the count is data dependent
+    return out[: min((nbits + 63) // 64, out.numel())], lengths, nbits
+
+
+def decode_variable(words, lengths, shape, dtype, out=None, stream=None):
+    """Decompress a variable-rate device stream (`words`, 64-bit words) with its
+    block index `lengths` (int16 tensor of raw uint16 bits, from
+    `encode_variable`) into a new (or given, possibly strided) CUDA tensor:
+    bit for bit what ``zfp_decompress`` returns in the mode that wrote the
+    stream.  The decoder needs no knowledge of the mode.  Asynchronous on
+    `stream`.  An index that does not belong to the stream cannot make the
+    decoder read outside `words`; the affected blocks decode to unspecified
+    values."""
+    import torch
+    if not words.is_cuda or not lengths.is_cuda:
+        raise ValueError("decode_variable: expects a device stream and a device index")
+    if lengths.element_size() != 2 or not lengths.is_contiguous() or not words.is_contiguous():
+        raise ValueError("decode_variable: lengths must be a contiguous 16-bit tensor, words contiguous")
+    if out is None:
+        out = torch.empty(tuple(int(s) for s in shape), dtype=dtype, device=words.device)
+    elif _broadcast(out):
+        raise ValueError("decode_variable: out is a broadcast view (zero stride); its elements alias each other")
+    t = type_code(out.dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError("decode_variable", 2)
+    nx, ny, nz = _extents(out.shape)
+    nblocks = 1
+    for s in out.shape:
+        nblocks *= (int(s) + 3) // 4
+    if lengths.numel() != nblocks:
+        raise ValueError(f"decode_variable: lengths has {lengths.numel()} entries, the array has {nblocks} blocks")
+    ws, ws_bytes = _variable_workspace(t, nx, ny, nz, words.device, stream, "decode_variable")
+    sx, sy, sz = _strides(out)
+    rc = library().cuzfp_hip_decode_variable(words.data_ptr(), words.numel() * words.element_size(),
+                                             lengths.data_ptr(), t, nx, ny, nz, sx, sy, sz, out.data_ptr(),
+                                             ws.data_ptr(), ws_bytes, _stream_handle(stream))
+    _check("decode_variable", rc)
+    return out
 
 
 def copy(src, dst, stream=None):

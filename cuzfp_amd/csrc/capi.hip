@@ -920,6 +920,94 @@ int cuzfp_hip_encode_region(const void* d_box, int type,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Variable-rate modes (variable_kernels.hpp)
+
+// floats only, maxbits a placeholder (the modes have no per-block budget)
+static int make_variable_problem(int type, unsigned nx, unsigned ny, unsigned nz, long long sx, long long sy,
+                                 long long sz, Problem* p) {
+  if (type == CUZFP_TYPE_INT32 || type == CUZFP_TYPE_INT64) return CUZFP_ERROR_UNSUPPORTED_TYPE;
+  return make_problem(type, nx, ny, nz, sx, sy, sz, 64, p);
+}
+
+static size_t variable_workspace_of(const Geometry& g) {
+  return 8 * ((size_t)g.nblocks + variable_tiles(g.nblocks));
+}
+
+int cuzfp_hip_accuracy_to_minexp(double tolerance) {
+  int emin = -1074;  // ZFP_MIN_EXP
+  if (tolerance > 0) {
+    // tolerance = x * 2^emin with 0.5 <= x < 1, then 2^(emin - 1) <= tolerance (zfp.c:444-458)
+    (void)frexp(tolerance, &emin);
+    emin--;
+  }
+  return emin;
+}
+
+size_t cuzfp_hip_variable_maximum_size(int type, unsigned nx, unsigned ny, unsigned nz, unsigned maxprec) {
+  Problem p;
+  if (make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p) != CUZFP_SUCCESS) return 0;
+  const unsigned prec = type == CUZFP_TYPE_FLOAT ? 32 : 64;
+  if (maxprec < 1 || maxprec > prec) return 0;
+  // zfp.c:369-397 with minbits 0 and maxbits ZFP_MAX_BITS (4171)
+  const unsigned values = 1u << (2 * p.dims);
+  const unsigned maxbits = std::min(min_bits(type) + values - 1 + values * maxprec, 4171u);
+  return ((148 + (size_t)p.g.nblocks * maxbits + 63) & ~(size_t)63) / 8;
+}
+
+size_t cuzfp_hip_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz) {
+  Problem p;
+  if (make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p) != CUZFP_SUCCESS) return 0;
+  return variable_workspace_of(p.g);
+}
+
+int cuzfp_hip_encode_variable(const void* d_data, int type, unsigned nx, unsigned ny, unsigned nz,
+                              long long sx, long long sy, long long sz, unsigned maxprec, int minexp,
+                              uint64_t* d_stream, size_t stream_capacity, uint16_t* d_lengths,
+                              uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                              hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, sx, sy, sz, &p);
+  if (rc) return rc;
+  const unsigned prec = type == CUZFP_TYPE_FLOAT ? 32 : 64;
+  if (maxprec < 1 || maxprec > prec) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_data || !d_lengths || !d_total_bits || !d_workspace) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_stream && stream_capacity) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_workspace & 7) || ((uintptr_t)d_stream & 7) || ((uintptr_t)d_total_bits & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (workspace_bytes < variable_workspace_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  uint64_t* offsets = (uint64_t*)d_workspace;
+  uint64_t* partials = offsets + p.g.nblocks;
+  const bool fast = p.fast_ok && ((uintptr_t)d_data & 15) == 0;
+  const uint64_t cap_words = stream_capacity / 8;
+  if (type == CUZFP_TYPE_FLOAT)
+    return launch_encode_variable_type<float>(p, d_data, fast, maxprec, minexp, d_stream, cap_words, d_lengths,
+                                              d_total_bits, offsets, partials, stream);
+  return launch_encode_variable_type<double>(p, d_data, fast, maxprec, minexp, d_stream, cap_words, d_lengths,
+                                             d_total_bits, offsets, partials, stream);
+}
+
+int cuzfp_hip_decode_variable(const uint64_t* d_stream, size_t stream_bytes, const uint16_t* d_lengths,
+                              int type, unsigned nx, unsigned ny, unsigned nz,
+                              long long sx, long long sy, long long sz, void* d_data,
+                              void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, sx, sy, sz, &p);
+  if (rc) return rc;
+  if (!d_data || !d_lengths || !d_workspace) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_stream && stream_bytes) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_workspace & 7) || ((uintptr_t)d_stream & 3)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (workspace_bytes < variable_workspace_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  uint64_t* offsets = (uint64_t*)d_workspace;
+  uint64_t* partials = offsets + p.g.nblocks;
+  const bool fast = p.fast_ok && ((uintptr_t)d_data & 15) == 0;
+  if (type == CUZFP_TYPE_FLOAT)
+    return launch_decode_variable_type<float>(p, d_stream, stream_bytes, d_lengths, fast, d_data, offsets, partials,
+                                              stream);
+  return launch_decode_variable_type<double>(p, d_stream, stream_bytes, d_lengths, fast, d_data, offsets, partials,
+                                             stream);
+}
+
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {
   if (!d_src || !d_dst || (bytes & 15) || (((uintptr_t)d_src | (uintptr_t)d_dst) & 15))
     return CUZFP_ERROR_INVALID_ARGUMENT;

@@ -117,4 +117,25 @@ int launch_encode_region_type(const Problem& p, const Region& r, const void* box
 // ranges are disjoint, m <= M.
 int launch_truncate(const uint64_t* src, uint64_t* dst, uint32_t nblocks, uint32_t M, uint32_t m, hipStream_t st);
 
+// The variable-rate modes (variable_kernels.hpp).  The workspace holds the
+// 64-bit bit offset of every block and the scan's tile sums (variable_tiles).
+//   scan: offsets = exclusive sum of lengths; the sum to *total unless null
+//   zero: the stream words two waves' segments can share (below cap_words)
+//   encode: lengths, *total, and the stream below cap_words (floats only)
+//   decode: no load outside [stream, stream + stream_bytes) whatever lengths holds
+constexpr uint32_t kVariableScanTile = 1024;  // lengths a scan workgroup
+inline uint32_t variable_tiles(uint32_t nblocks) { return (nblocks + kVariableScanTile - 1) / kVariableScanTile; }
+int launch_variable_scan(const uint16_t* lengths, uint32_t nblocks, uint64_t* offsets, uint64_t* partials,
+                         uint64_t* total, hipStream_t st);
+int launch_variable_zero(uint64_t* stream, uint64_t cap_words, const uint64_t* offsets, uint32_t nblocks,
+                         const uint64_t* total, hipStream_t st);
+template <typename Scalar>
+int launch_encode_variable_type(const Problem& p, const void* data, bool fast, uint32_t maxprec, int minexp,
+                                uint64_t* stream, uint64_t cap_words, uint16_t* lengths, uint64_t* total,
+                                uint64_t* offsets, uint64_t* partials, hipStream_t st);
+template <typename Scalar>
+int launch_decode_variable_type(const Problem& p, const uint64_t* stream, size_t stream_bytes,
+                                const uint16_t* lengths, bool fast, void* out, uint64_t* offsets,
+                                uint64_t* partials, hipStream_t st);
+
 }  // namespace cuzfp

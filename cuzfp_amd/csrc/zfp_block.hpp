@@ -2493,4 +2493,85 @@ ZFP_HD bool decode_block(Scalar* f, unsigned maxbits, Reader& rd) {
 
 ZFP_HD int pad_src(int i, int n) { return i < n ? i : (i == 3 ? 0 : n - 1); }
 
+// ---------------------------------------------------------------------------
+// Variable-rate modes: fixed precision (zfp_stream_set_precision) and fixed
+// accuracy (zfp_stream_set_accuracy).  Both set maxprec and minexp and leave
+// the budget at ZFP_MAX_BITS, which never binds, so a block is coded through
+// plane intprec - p, p = precision(emax, maxprec, minexp), and ends there: it
+// is the first L bits of the same block coded without a budget (the coder is
+// embedded, see rerate.hpp), or the single bit 0 when p == 0 or the block is
+// all zero.  L follows from the bit planes in closed form, below; the kernels
+// (variable_kernels.hpp) compute it in a pass of its own, scan it to bit
+// offsets, and then run encode_block unchanged behind a writer whose limit is
+// the lane's own L.
+
+// precision() with the mode's parameters (codec1.c:8-11, codec2.c:131-136,
+// codec3.c:92-97)
+template <int DIMS>
+ZFP_HD unsigned precision_variable(int emax, unsigned maxprec, int minexp) {
+  int p = emax - minexp + 2 * (DIMS + 1);
+  p = p < 0 ? 0 : p;
+  return (unsigned)p < maxprec ? (unsigned)p : maxprec;
+}
+
+// Bits of plane x coded with n coefficients already significant, without a
+// budget (encode.c:133-150); n becomes the count after the plane.  With r =
+// x >> n the plane's not yet significant part: the n verbatim bits; for every
+// one of r a "1" group test; one bit for each position up to r's top one (the
+// one at position N - 1 is implied); and the closing "0" test unless the
+// plane's end was reached.
+template <int DIMS>
+ZFP_HD unsigned plane_bits(uint64_t x, unsigned& n) {
+  constexpr unsigned N = 1u << (2 * DIMS);
+  const uint64_t r = n < N ? x >> n : 0ull;
+  const unsigned bl = r ? 64u - (unsigned)__builtin_clzll(r) : 0u;
+  const unsigned nn = n + bl;
+  const unsigned imp = (bl != 0u && nn == N) ? 1u : 0u;
+  const unsigned len = n + (unsigned)__builtin_popcountll(r) + bl - imp + (nn < N ? 1u : 0u);
+  n = nn;
+  return len;
+}
+
+// Length in bits of block f in a variable-rate mode (what
+// zfp_encode_block_{float,double}_{1,2,3} returns with the stream's maxprec
+// and minexp set by the mode): 1 for the zero-block form, else the exponent
+// field and planes intprec - 1 .. intprec - p.
+template <typename Scalar, int DIMS>
+ZFP_HD unsigned block_length(const Scalar* f, unsigned maxprec, int minexp) {
+  typedef traits<Scalar> T;
+  typedef typename T::UInt UInt;
+  constexpr int N = 1 << (2 * DIMS);
+  static_assert(!T::is_int, "the variable-rate modes are defined for floats");
+  const int emax = fp<Scalar>::template emax<N>(f);
+  const unsigned p = precision_variable<DIMS>(emax, maxprec, minexp);
+  // encode.c:199-215: e = p ? emax + ebias : 0, and e == 0 writes the one bit
+  if (!p || emax + T::ebias == 0) return 1u;
+  const Scalar s = (Scalar)fp<Scalar>::pow2(T::prec - 2 - emax);
+  UInt q[N], u[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) q[i] = (UInt)fp<Scalar>::to_int(s * f[i]);
+  fwd_xform<DIMS>(q);
+  permute_fwd_add<DIMS>(q, u, nbmask<UInt>::value, make_seq<N>());
+  planes<UInt, DIMS> P;
+  P.template load<true>(u);
+  unsigned len = 1u + T::ebits, n = 0;
+  // every plane with a compile-time number (the plane words are registers);
+  // the planes below intprec - p add nothing
+#pragma unroll
+  for (int k = T::prec - 1; k >= 0; k--) {
+    unsigned nn = n;
+    const unsigned l = plane_bits<DIMS>((uint64_t)P.get(k), nn);
+    const bool coded = (unsigned)k + p >= (unsigned)T::prec;
+    len += coded ? l : 0u;
+    n = coded ? nn : n;
+  }
+  return len;
+}
+
+// The most bits a block takes at maxprec (zfp.c zfp_stream_maximum_size)
+template <typename Scalar, int DIMS>
+ZFP_HD constexpr unsigned max_block_bits(unsigned maxprec) {
+  return 1u + traits<Scalar>::ebits + ((1u << (2 * DIMS)) - 1u) + (maxprec << (2 * DIMS));
+}
+
 }  // namespace cuzfp

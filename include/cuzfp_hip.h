@@ -235,6 +235,64 @@ int cuzfp_hip_decode_region_prefix(const uint64_t* d_stream, size_t stream_bytes
                                    long long sx, long long sy, long long sz,
                                    void* d_out, hipStream_t stream);
 
+/* Not reference entry points (callers test CUZFP_HIP_HAS_VARIABLE): zfp's
+ * variable-rate modes, fixed precision (zfp_stream_set_precision) and fixed
+ * accuracy (zfp_stream_set_accuracy), float and double only (integer types:
+ * CUZFP_ERROR_UNSUPPORTED_TYPE, as zfp 0.5.0's zfp_compress).
+ *
+ * The stream is byte-identical to CPU zfp 0.5.0's zfp_compress in that mode:
+ * the blocks in raster order, back to back without padding, flushed with zero
+ * bits to a 64-bit word, no header.  Block b takes lengths[b] bits (uint16,
+ * at most 4171); the index `lengths` is a side array the caller keeps with
+ * the stream (0.25 bit a value in 3D, 1 in 2D, 4 in 1D) -- it is what lets the
+ * decoder start every block in parallel.
+ *
+ * A mode is the pair (maxprec, minexp):
+ *   fixed precision p:  maxprec = p (1 .. 32 float, 1 .. 64 double), minexp = -1074
+ *   fixed accuracy tol: maxprec = the type's precision (32 / 64),
+ *                       minexp = cuzfp_hip_accuracy_to_minexp(tol)
+ *
+ * cuzfp_hip_accuracy_to_minexp: zfp_stream_set_accuracy's rule, floor(log2
+ *   tolerance) by frexp, or -1074 (ZFP_MIN_EXP) for a tolerance <= 0.
+ * cuzfp_hip_variable_maximum_size: the worst-case stream bytes
+ *   (zfp_stream_maximum_size in these modes, its header allowance included,
+ *   as cuzfp_hip_maximum_size); 0 for invalid arguments.
+ * cuzfp_hip_variable_workspace_bytes: bytes of device scratch either call
+ *   below needs (the blocks' 64-bit offsets and the scan's partial sums); the
+ *   caller owns it (8-byte aligned); 0 for invalid arguments.
+ *
+ * cuzfp_hip_encode_variable: asynchronous on `stream`, no allocation, no
+ *   synchronisation (six kernel launches: lengths, a three-launch scan, a
+ *   zero fill, the coder).  Strides as cuzfp_hip_encode.  Writes
+ *   d_lengths[0 .. nblocks) and the 64-bit bit count *d_total_bits (both device
+ *   memory: the count depends on the data), and the stream's ceil(total / 64)
+ *   words, no byte past them and none at or past stream_capacity: if the
+ *   stream does not fit, the lengths and the count are still right and the
+ *   stream's contents are unspecified (cuzfp_hip_variable_maximum_size bytes
+ *   always fit).  maxprec outside 1 .. the type's precision, a null pointer or
+ *   a workspace below cuzfp_hip_variable_workspace_bytes:
+ *   CUZFP_ERROR_INVALID_ARGUMENT.
+ * cuzfp_hip_decode_variable: the same launch properties (a three-launch scan
+ *   of the lengths, the decoder).  Block b is decoded from the sum of the
+ *   lengths before it with a budget of d_lengths[b] bits; the result is what
+ *   zfp_decompress returns in the mode that wrote the stream.  The index is
+ *   not trusted: whatever it holds, nothing outside [d_stream, d_stream +
+ *   stream_bytes) is read; blocks whose entries are wrong decode to
+ *   unspecified values. */
+#define CUZFP_HIP_HAS_VARIABLE 1
+int cuzfp_hip_accuracy_to_minexp(double tolerance);
+size_t cuzfp_hip_variable_maximum_size(int type, unsigned nx, unsigned ny, unsigned nz, unsigned maxprec);
+size_t cuzfp_hip_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz);
+int cuzfp_hip_encode_variable(const void* d_data, int type, unsigned nx, unsigned ny, unsigned nz,
+                              long long sx, long long sy, long long sz, unsigned maxprec, int minexp,
+                              uint64_t* d_stream, size_t stream_capacity, uint16_t* d_lengths,
+                              uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                              hipStream_t stream);
+int cuzfp_hip_decode_variable(const uint64_t* d_stream, size_t stream_bytes, const uint16_t* d_lengths,
+                              int type, unsigned nx, unsigned ny, unsigned nz,
+                              long long sx, long long sy, long long sz, void* d_data,
+                              void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,
