@@ -22,6 +22,7 @@ __all__ = [
     "library", "library_path", "rate_to_maxbits", "stream_bytes", "maximum_size",
     "encode", "decode", "decode_region", "encode_region", "truncate", "compress_host", "decompress_host", "type_code",
     "encode_variable", "decode_variable", "accuracy_to_minexp", "variable_maximum_size",
+    "variable_index", "decode_region_variable",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -96,6 +97,13 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_encode_variable.argtypes = [vp, i, u, u, u, ll, ll, ll, u, i, vp, sz, vp, vp, vp, sz, vp]
     lib.cuzfp_hip_decode_variable.restype = i
     lib.cuzfp_hip_decode_variable.argtypes = [vp, sz, vp, i, u, u, u, ll, ll, ll, vp, vp, sz, vp]
+    lib.cuzfp_hip_variable_index_bytes.restype = sz
+    lib.cuzfp_hip_variable_index_bytes.argtypes = [i, u, u, u]
+    lib.cuzfp_hip_variable_index.restype = i
+    lib.cuzfp_hip_variable_index.argtypes = [vp, i, u, u, u, vp, sz, vp, sz, vp]
+    lib.cuzfp_hip_decode_region_variable.restype = i
+    lib.cuzfp_hip_decode_region_variable.argtypes = [vp, sz, vp, vp, sz, i, u, u, u, u, u, u, u, u, u, ll, ll, ll,
+                                                     vp, vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -466,7 +474,7 @@ def encode_variable(x, precision=None, tolerance=None, out=None, stream=None):
     return out[: min((nbits + 63) // 64, out.numel())], lengths, nbits
 
 
-def decode_variable(words, lengths, shape, dtype, out=None, stream=None):
+def decode_variable(words, lengths, shape, dtype, out=None, stream=None, index=None):
     """Decompress a variable-rate device stream (`words`, 64-bit words) with its
     block index `lengths` (int16 tensor of raw uint16 bits, from
     `encode_variable`) into a new (or given, possibly strided) CUDA tensor:
@@ -474,8 +482,16 @@ def decode_variable(words, lengths, shape, dtype, out=None, stream=None):
     stream.  The decoder needs no knowledge of the mode.  Asynchronous on
     `stream`.  An index that does not belong to the stream cannot make the
     decoder read outside `words`; the affected blocks decode to unspecified
-    values."""
+    values.
+
+    `index` (from `variable_index`) decodes through `decode_region_variable`
+    with the whole array as the box: one launch, no scan of the lengths and no
+    workspace.  None scans the lengths on every call."""
     import torch
+    if index is not None:
+        shape = tuple(int(s) for s in (shape if out is None else out.shape))
+        return decode_region_variable(words, lengths, index, shape, dtype, (0,) * len(shape), shape, out=out,
+                                      stream=stream)
     if not words.is_cuda or not lengths.is_cuda:
         raise ValueError("decode_variable: expects a device stream and a device index")
     if lengths.element_size() != 2 or not lengths.is_contiguous() or not words.is_contiguous():
@@ -499,6 +515,100 @@ def decode_variable(words, lengths, shape, dtype, out=None, stream=None):
                                              lengths.data_ptr(), t, nx, ny, nz, sx, sy, sz, out.data_ptr(),
                                              ws.data_ptr(), ws_bytes, _stream_handle(stream))
     _check("decode_variable", rc)
+    return out
+
+
+def _block_count(shape) -> int:
+    n = 1
+    for s in shape:
+        n *= (int(s) + 3) // 4
+    return n
+
+
+def variable_index(lengths, shape, dtype, out=None, stream=None):
+    """The offset index of a variable-rate stream, from its `lengths` (the
+    int16 tensor of `encode_variable`): an int64 tensor of T + 1 entries, T =
+    ceil(nblocks / 64), entry t the bit offset of block 64 t and entry T the
+    stream's bit count.  It is a sixteenth of `lengths` and is kept with the
+    stream: `decode_region_variable` and ``decode_variable(index=)`` find any
+    block through it without scanning the lengths.  `lengths` may start at any
+    element of a larger tensor (2-byte alignment is enough).  Asynchronous on
+    `stream`; the scan's scratch is allocated on that stream."""
+    import torch
+    if not lengths.is_cuda:
+        raise ValueError("variable_index: expects a device index")
+    if lengths.element_size() != 2 or not lengths.is_contiguous():
+        raise ValueError("variable_index: lengths must be a contiguous 16-bit tensor")
+    shape = tuple(int(s) for s in shape)
+    nx, ny, nz = _extents(shape)
+    t = type_code(dtype)
+    n = library().cuzfp_hip_variable_index_bytes(t, nx, ny, nz)
+    if n == 0:
+        raise CodecError("variable_index", 2 if t in (TYPE_INT32, TYPE_INT64) else 1)
+    if lengths.numel() != _block_count(shape):
+        raise ValueError(f"variable_index: lengths has {lengths.numel()} entries, the array has "
+                         f"{_block_count(shape)} blocks")
+    ws, ws_bytes = _variable_workspace(t, nx, ny, nz, lengths.device, stream, "variable_index")
+    if out is None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(lengths.device)):
+            out = torch.empty(n // 8, dtype=torch.int64, device=lengths.device)
+    elif not out.is_cuda or not out.is_contiguous() or out.element_size() != 8 or out.numel() < n // 8:
+        raise ValueError(f"variable_index: out must be a contiguous device tensor of at least {n // 8} 64-bit words")
+    rc = library().cuzfp_hip_variable_index(lengths.data_ptr(), t, nx, ny, nz, out.data_ptr(), out.numel() * 8,
+                                            ws.data_ptr(), ws_bytes, _stream_handle(stream))
+    _check("variable_index", rc)
+    return out[: n // 8]
+
+
+def decode_region_variable(words, lengths, index, shape, dtype, origin, extent, out=None, stream=None):
+    """Decompress the box ``origin .. origin + extent`` (slowest first, like
+    `shape`) of the array a variable-rate device stream holds into a new (or
+    given, possibly strided) CUDA tensor of shape `extent`: bit for bit the box
+    of `decode_variable`'s array.  `index` is `variable_index` of `lengths`.
+
+    One kernel launch that reads only the box's blocks: no scan, no scratch, no
+    allocation when `out` is given, no synchronisation (it can be captured into
+    a graph).  Neither `index` nor `lengths` can make the decoder read outside
+    `words` or write outside the box; blocks whose entries are wrong decode to
+    unspecified values."""
+    import torch
+    shape = tuple(int(s) for s in shape)
+    origin = tuple(int(o) for o in origin)
+    extent = tuple(int(e) for e in extent)
+    nx, ny, nz = _extents(shape)
+    if len(origin) != len(shape) or len(extent) != len(shape):
+        raise ValueError(f"decode_region_variable: origin {origin} and extent {extent} must have "
+                         f"the rank of shape {shape}")
+    if any(o < 0 for o in origin) or any(e <= 0 for e in extent):
+        raise ValueError("decode_region_variable: origin must be non-negative and extent positive")
+    if not words.is_cuda or not lengths.is_cuda or not index.is_cuda:
+        raise ValueError("decode_region_variable: expects a device stream and device indices")
+    if lengths.element_size() != 2 or not lengths.is_contiguous() or not words.is_contiguous():
+        raise ValueError("decode_region_variable: lengths must be a contiguous 16-bit tensor, words contiguous")
+    if index.element_size() != 8 or not index.is_contiguous():
+        raise ValueError("decode_region_variable: index must be a contiguous tensor of 64-bit words")
+    if out is None:
+        out = torch.empty(extent, dtype=dtype, device=words.device)
+    elif _broadcast(out):
+        raise ValueError("decode_region_variable: out is a broadcast view (zero stride); its elements alias "
+                         "each other")
+    elif tuple(out.shape) != extent:
+        raise ValueError(f"decode_region_variable: out has shape {tuple(out.shape)}, expected {extent}")
+    t = type_code(out.dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError("decode_region_variable", 2)
+    if lengths.numel() != _block_count(shape):
+        raise ValueError(f"decode_region_variable: lengths has {lengths.numel()} entries, the array has "
+                         f"{_block_count(shape)} blocks")
+    ox, oy, oz = _extents(origin)
+    ex, ey, ez = _extents(extent)
+    sx, sy, sz = _strides(out)
+    rc = library().cuzfp_hip_decode_region_variable(words.data_ptr(), words.numel() * words.element_size(),
+                                                    lengths.data_ptr(), index.data_ptr(),
+                                                    index.numel() * index.element_size(), t, nx, ny, nz,
+                                                    ox, oy, oz, ex, ey, ez, sx, sy, sz, out.data_ptr(),
+                                                    _stream_handle(stream))
+    _check("decode_region_variable", rc)
     return out
 
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "launch.hpp"
+#include "variable_index.hpp"
 
 namespace cuzfp {
 
@@ -1006,6 +1007,71 @@ int cuzfp_hip_decode_variable(const uint64_t* d_stream, size_t stream_bytes, con
                                               stream);
   return launch_decode_variable_type<double>(p, d_stream, stream_bytes, d_lengths, fast, d_data, offsets, partials,
                                              stream);
+}
+
+// ---------------------------------------------------------------------------
+// The offset index and the sub-box decoder that reads it (variable_index.hpp,
+// region_variable_kernels.hpp)
+
+static size_t variable_index_bytes_of(const Geometry& g) {
+  return 8 * ((size_t)variable_index_tiles(g.nblocks) + 1);
+}
+
+size_t cuzfp_hip_variable_index_bytes(int type, unsigned nx, unsigned ny, unsigned nz) {
+  Problem p;
+  if (make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p) != CUZFP_SUCCESS) return 0;
+  return variable_index_bytes_of(p.g);
+}
+
+int cuzfp_hip_variable_index(const uint16_t* d_lengths, int type, unsigned nx, unsigned ny, unsigned nz,
+                             uint64_t* d_index, size_t index_bytes, void* d_workspace, size_t workspace_bytes,
+                             hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
+  if (rc) return rc;
+  if (!d_lengths || !d_index || !d_workspace) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_lengths & 1) || ((uintptr_t)d_index & 7) || ((uintptr_t)d_workspace & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (index_bytes < variable_index_bytes_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (workspace_bytes < variable_workspace_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  uint64_t* offsets = (uint64_t*)d_workspace;
+  return launch_variable_index(d_lengths, p.g.nblocks, d_index, offsets, offsets + p.g.nblocks, stream);
+}
+
+int cuzfp_hip_decode_region_variable(const uint64_t* d_stream, size_t stream_bytes, const uint16_t* d_lengths,
+                                     const uint64_t* d_index, size_t index_bytes, int type,
+                                     unsigned nx, unsigned ny, unsigned nz,
+                                     unsigned ox, unsigned oy, unsigned oz,
+                                     unsigned ex, unsigned ey, unsigned ez,
+                                     long long sx, long long sy, long long sz, void* d_out, hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
+  if (rc) return rc;
+  if (!d_out || !d_stream || !d_lengths || !d_index) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_stream & 3) || ((uintptr_t)d_lengths & 1) || ((uintptr_t)d_index & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the box rules of cuzfp_hip_decode_region
+  if (p.dims < 2 && (oy || ey)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 3 && (oz || ez)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 2) ey = 1;
+  if (p.dims < 3) ez = 1;
+  if (!ex || !ey || !ez) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ox >= p.g.nx || ex > p.g.nx - ox || oy >= p.g.ny || ey > p.g.ny - oy || oz >= p.g.nz ||
+      ez > p.g.nz - oz)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (index_bytes < variable_index_bytes_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // (no stream_bytes test: the stream's length is in the index, on the device;
+  // the kernel loads nothing at or past stream_bytes)
+  const Region r = make_region(p.g, ox, oy, oz, ex, ey, ez, sx, sy, sz);
+  // a block-aligned box into a contiguous, 16-byte aligned array: the row stores
+  const bool fast = !((ox | ex) & 3) && (p.dims < 2 || !((oy | ey) & 3)) && (p.dims < 3 || !((oz | ez) & 3)) &&
+                    r.sx == 1 && r.sy == (long long)ex && r.sz == (long long)ex * ey &&
+                    ((uintptr_t)d_out & 15) == 0;
+  if (type == CUZFP_TYPE_FLOAT)
+    return launch_decode_region_variable_type<float>(p, r, d_stream, stream_bytes, d_lengths, d_index, fast, d_out,
+                                                     stream);
+  return launch_decode_region_variable_type<double>(p, r, d_stream, stream_bytes, d_lengths, d_index, fast, d_out,
+                                                    stream);
 }
 
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {

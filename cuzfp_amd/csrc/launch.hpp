@@ -138,4 +138,19 @@ int launch_decode_variable_type(const Problem& p, const uint64_t* stream, size_t
                                 const uint16_t* lengths, bool fast, void* out, uint64_t* offsets,
                                 uint64_t* partials, hipStream_t st);
 
+// The offset index of a variable-rate stream and the sub-box decoder that reads
+// it (variable_index.hpp, region_variable_kernels.hpp).
+//   index: index[t] = the bit offset of block 64 t, index[T] = the total; the
+//          scan's offsets and partials are the variable-rate workspace
+//   decode: one launch; `out` is the box's element (0, 0, 0); fast as
+//           launch_decode_region_type; no load outside [stream, stream +
+//           stream_bytes), lengths[0 .. nblocks) and index[0 .. T) whatever
+//           index and lengths hold
+int launch_variable_index(const uint16_t* lengths, uint32_t nblocks, uint64_t* index, uint64_t* offsets,
+                          uint64_t* partials, hipStream_t st);
+template <typename Scalar>
+int launch_decode_region_variable_type(const Problem& p, const Region& r, const uint64_t* stream, size_t stream_bytes,
+                                       const uint16_t* lengths, const uint64_t* index, bool fast, void* out,
+                                       hipStream_t st);
+
 }  // namespace cuzfp

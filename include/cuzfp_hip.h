@@ -293,6 +293,53 @@ int cuzfp_hip_decode_variable(const uint64_t* d_stream, size_t stream_bytes, con
                               long long sx, long long sy, long long sz, void* d_data,
                               void* d_workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* Not reference entry points (callers test CUZFP_HIP_HAS_VARIABLE_REGION):
+ * random access into a variable-rate stream.  cuzfp_hip_decode_variable scans
+ * all the lengths on every call and decodes the whole array; with a
+ * persistent offset index, built once and kept beside `lengths`, a sub-box is
+ * decoded in one launch that reads only the box's blocks.
+ *
+ * The index is one uint64 per tile of 64 raster-consecutive blocks plus the
+ * total, T = ceil(nblocks / 64):
+ *   index[t] = sum of lengths[0 .. 64 t)   t = 0 .. T - 1
+ *   index[T] = sum of all lengths (the stream's bit count)
+ * (the raw uint16 values summed), 8 (T + 1) bytes: a sixteenth of `lengths`.
+ * Block b starts at bit index[b / 64] + the sum of lengths[64 (b / 64) .. b).
+ *
+ * cuzfp_hip_variable_index_bytes: 8 (T + 1); 0 for invalid dimensions and
+ *   integer types.
+ * cuzfp_hip_variable_index: asynchronous on `stream`, no allocation, no
+ *   synchronisation (the three-launch scan into the workspace, one launch that
+ *   picks every 64th offset).  d_lengths needs no alignment beyond a
+ *   uint16's; d_index and the workspace 8 bytes.  The workspace is
+ *   cuzfp_hip_variable_workspace_bytes.  A null or misaligned pointer, a short
+ *   index_bytes or workspace: CUZFP_ERROR_INVALID_ARGUMENT before any launch;
+ *   integer types CUZFP_ERROR_UNSUPPORTED_TYPE.
+ * cuzfp_hip_decode_region_variable: the box origin + extent of the array the
+ *   stream holds into d_out, bit for bit the box of cuzfp_hip_decode_variable's
+ *   array.  One kernel launch, no workspace, no allocation, no
+ *   synchronisation; it can be captured into a graph.  Box, stride and
+ *   unused-dimension rules and their status codes are
+ *   cuzfp_hip_decode_region's (d_out is the box's element (0, 0, 0), strides 0 =
+ *   contiguous out[ez][ey][ex]); a null or misaligned pointer (d_stream 4
+ *   bytes, d_index 8) or a short index_bytes: CUZFP_ERROR_INVALID_ARGUMENT.
+ *   stream_bytes is the bound of the loads, not checked against the index.
+ *   Neither the index nor the lengths are trusted: whatever they hold, nothing
+ *   outside [d_stream, d_stream + stream_bytes), d_lengths[0 .. nblocks) and
+ *   d_index[0 .. T) is read and nothing outside the box is written; blocks
+ *   whose entries are wrong decode to unspecified values. */
+#define CUZFP_HIP_HAS_VARIABLE_REGION 1
+size_t cuzfp_hip_variable_index_bytes(int type, unsigned nx, unsigned ny, unsigned nz);
+int cuzfp_hip_variable_index(const uint16_t* d_lengths, int type, unsigned nx, unsigned ny, unsigned nz,
+                             uint64_t* d_index, size_t index_bytes,
+                             void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+int cuzfp_hip_decode_region_variable(const uint64_t* d_stream, size_t stream_bytes,
+                                     const uint16_t* d_lengths, const uint64_t* d_index, size_t index_bytes,
+                                     int type, unsigned nx, unsigned ny, unsigned nz,
+                                     unsigned ox, unsigned oy, unsigned oz,
+                                     unsigned ex, unsigned ey, unsigned ez,
+                                     long long sx, long long sy, long long sz, void* d_out, hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,

@@ -3,7 +3,7 @@ tool, not a test).
 
   python tools/time_variable.py [--out FILE]
 
-The 256^3 f32 polynomial field at tolerances 1e-2 and 1e-4, five legs:
+The 256^3 f32 polynomial field at tolerances 1e-2 and 1e-4, eleven legs:
 
   encode_variable  cuzfp_hip_encode_variable (lengths, scan, zero, coder) into
                    preallocated buffers -- no read-back of the bit count
@@ -11,12 +11,22 @@ The 256^3 f32 polynomial field at tolerances 1e-2 and 1e-4, five legs:
   encode, decode   the fixed-rate calls at the maxbits whose stream is nearest
                    in size to the variable one (the mean block length, rounded)
   copy             cz.copy of the uncompressed array: the bandwidth floor
+  variable_index   cuzfp_hip_variable_index (scan, pick) of the stream's lengths
+  region_variable_brick, _brick_off
+                   cuzfp_hip_decode_region_variable of a 64^3 brick at (64, 64, 64)
+                   (block aligned) and at (65, 66, 67), one launch each
+  region_variable_whole
+                   the same call with the whole array as the box: what
+                   decode_variable(index=) runs, beside decode_variable
+  region_fixed_brick, _brick_off
+                   cz.decode_region of the same bricks of the fixed-rate stream
 
 Each leg is a hipGraph of `reps` calls, timed with device events after a
 warm-up replay; the legs are replayed in turn, round after round, in one
 process, for as many rounds as make every leg run for at least --seconds in
 all; the median round is reported with the fastest and slowest.  GB/s are
-uncompressed bytes over the call's time.  The variable stream's round-trip
+the uncompressed bytes the call produces (the brick's for the brick legs)
+over the call's time.  The variable stream's round-trip
 error is reported beside the tolerance.  Prints one JSON line per tolerance
 and writes them to --out.
 """
@@ -80,7 +90,35 @@ def main():
                                                cz._stream_handle(None))
             assert rc == 0
 
-        legs = {"encode_variable": enc_var, "decode_variable": dec_var,
+        index = cz.variable_index(lengths, shape, torch.float32)
+        vidx = torch.empty_like(index)
+        brick = min(64, a.size // 2)
+        bout = torch.empty((brick,) * 3, dtype=torch.float32, device=x.device)
+        aligned, off = (brick,) * 3, (brick + 1, brick + 2, brick + 3)
+        assert torch.equal(cz.decode_region_variable(words, lengths, index, shape, torch.float32, off, (brick,) * 3),
+                           back[tuple(slice(o, o + brick) for o in off)])
+        assert torch.equal(cz.decode_variable(words, lengths, shape, torch.float32, index=index), back)
+
+        def build_index():
+            rc = lib.cuzfp_hip_variable_index(lengths.data_ptr(), 3, nx, ny, nz, vidx.data_ptr(), vidx.numel() * 8,
+                                              ws.data_ptr(), ws_bytes, cz._stream_handle(None))
+            assert rc == 0
+
+        def region_var(origin, extent, out):
+            return lambda: cz.decode_region_variable(words, lengths, index, shape, torch.float32, origin, extent,
+                                                     out=out)
+
+        def region_fixed(origin):
+            return lambda: cz.decode_region(fixed, shape, torch.float32, mb, origin, (brick,) * 3, out=bout)
+
+        produced = {leg: bout.numel() * 4 for leg in ("region_variable_brick", "region_variable_brick_off",
+                                                      "region_fixed_brick", "region_fixed_brick_off")}
+        legs = {"variable_index": build_index,
+                "region_variable_brick": region_var(aligned, (brick,) * 3, bout),
+                "region_variable_brick_off": region_var(off, (brick,) * 3, bout),
+                "region_variable_whole": region_var((0, 0, 0), shape, y),
+                "region_fixed_brick": region_fixed(aligned), "region_fixed_brick_off": region_fixed(off),
+                "encode_variable": enc_var, "decode_variable": dec_var,
                 "encode": lambda: cz.encode(x, mb, out=fixed),
                 "decode": lambda: cz.decode(fixed, shape, torch.float32, mb, out=y),
                 "copy": lambda: cz.copy(x, cb)}
@@ -103,7 +141,7 @@ def main():
             once[leg] = e0.elapsed_time(e1) / 1000
             graphs[leg] = g
         assert torch.equal(vlen, lengths) and int(vtot.item()) == nbits
-        assert torch.equal(vout[: words.numel()], words)
+        assert torch.equal(vout[: words.numel()], words) and torch.equal(vidx, index)
         rounds = max(5, min(a.max_rounds, int(a.seconds / min(once.values())) + 1))
         t = {leg: [] for leg in graphs}
         for _ in range(rounds):
@@ -116,6 +154,7 @@ def main():
                 t[leg].append(e0.elapsed_time(e1) / a.reps * 1000)
         rec = {"config": "3D f32 %d^3 polynomial" % a.size, "tolerance": tol, "max_abs_error": err,
                "variable_stream_bytes": words.numel() * 8, "index_bytes": lengths.numel() * 2,
+               "offset_index_bytes": index.numel() * 8, "brick": brick,
                "variable_ratio": round(raw / (words.numel() * 8), 2),
                "variable_ratio_with_index": round(raw / (words.numel() * 8 + lengths.numel() * 2), 2),
                "fixed_maxbits": mb, "fixed_stream_bytes": fixed.numel() * 8,
@@ -127,7 +166,7 @@ def main():
             med = v[len(v) // 2]
             rec[leg + "_us"] = round(med, 2)
             rec[leg + "_us_min_max"] = [round(v[0], 2), round(v[-1], 2)]
-            rec[leg + "_GBps"] = round(raw / med / 1e3, 1)
+            rec[leg + "_GBps"] = round(produced.get(leg, raw) / med / 1e3, 1)
         results.append(rec)
         print(json.dumps(rec), flush=True)
         del graphs
