@@ -22,7 +22,7 @@ __all__ = [
     "library", "library_path", "rate_to_maxbits", "stream_bytes", "maximum_size",
     "encode", "decode", "decode_region", "encode_region", "truncate", "compress_host", "decompress_host", "type_code",
     "encode_variable", "decode_variable", "accuracy_to_minexp", "variable_maximum_size",
-    "variable_index", "decode_region_variable",
+    "variable_index", "decode_region_variable", "truncate_variable",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -104,6 +104,10 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_decode_region_variable.restype = i
     lib.cuzfp_hip_decode_region_variable.argtypes = [vp, sz, vp, vp, sz, i, u, u, u, u, u, u, u, u, u, ll, ll, ll,
                                                      vp, vp]
+    lib.cuzfp_hip_truncate_variable_workspace_bytes.restype = sz
+    lib.cuzfp_hip_truncate_variable_workspace_bytes.argtypes = [i, u, u, u]
+    lib.cuzfp_hip_truncate_variable.restype = i
+    lib.cuzfp_hip_truncate_variable.argtypes = [vp, sz, vp, i, u, u, u, u, i, u, i, vp, sz, vp, vp, vp, sz, vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -610,6 +614,100 @@ def decode_region_variable(words, lengths, index, shape, dtype, origin, extent, 
                                                     _stream_handle(stream))
     _check("decode_region_variable", rc)
     return out
+
+
+def _variable_mode(where, type_prec, precision, tolerance, names):
+    """(maxprec, minexp) of exactly one of a precision and a tolerance."""
+    if (precision is None) == (tolerance is None):
+        raise ValueError(f"{where}: give exactly one of {names[0]} and {names[1]}")
+    if precision is not None:
+        if int(precision) != precision:
+            raise ValueError(f"{where}: {names[0]} {precision!r} is not a whole number of bit planes")
+        maxprec, minexp = int(precision), -1074
+    else:
+        maxprec, minexp = type_prec, accuracy_to_minexp(tolerance)
+    if not 1 <= maxprec <= type_prec:
+        raise CodecError(where, 1)
+    return maxprec, minexp
+
+
+def truncate_variable(words, lengths, shape, dtype, *, from_precision=None, from_tolerance=None,
+                      precision=None, tolerance=None, out=None, stream=None, size_only=False):
+    """The stream of the same array in a coarser variable-rate mode, cut from
+    the device stream `words` with its index `lengths` (both from
+    `encode_variable`) without decoding; returns ``(words, lengths, nbits)``
+    like `encode_variable`.
+
+    Exactly one of `from_precision` and `from_tolerance` names the mode that
+    wrote `words`, exactly one of `precision` and `tolerance` the new mode.
+    With a mode as the pair (maxprec, minexp) -- precision p: (p, -1074);
+    tolerance t: (the type's 32 / 64, accuracy_to_minexp(t)) -- the new mode
+    must have maxprec no higher and minexp no lower than the source's, so a
+    full-precision stream can be cut to any precision or tolerance.
+
+    zfp's coder is embedded, so every new block is a prefix of the old one --
+    or the single bit 0 where the new mode codes no plane of it -- and the
+    result is byte for byte what `encode_variable` of the original array gives
+    in the new mode: it feeds `decode_variable`, `variable_index` and
+    `decode_region_variable` unchanged.  Widening is not offered: the planes a
+    finer mode codes are not in the stream.
+
+    `out` (64-bit words, not overlapping `words`) is allocated at
+    `variable_maximum_size` of the new maxprec when None; a shorter `out` is
+    never written past its end, but then holds no valid stream if nbits exceeds
+    it.  ``size_only=True`` computes the new lengths and the bit count alone and
+    returns ``(None, lengths, nbits)``.  An index that does not belong to the
+    stream cannot make the call read outside `words` and `lengths` or write
+    outside its outputs.  Asynchronous on `stream` except for one
+    synchronisation to read the count, as `encode_variable`."""
+    import torch
+    t = type_code(dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError("truncate_variable", 2)
+    type_prec = 32 if t == TYPE_FLOAT else 64
+    maxprec, minexp = _variable_mode("truncate_variable", type_prec, from_precision, from_tolerance,
+                                     ("from_precision", "from_tolerance"))
+    new_maxprec, new_minexp = _variable_mode("truncate_variable", type_prec, precision, tolerance,
+                                             ("precision", "tolerance"))
+    if new_maxprec > maxprec or new_minexp < minexp:
+        raise ValueError(f"truncate_variable: the mode (maxprec {new_maxprec}, minexp {new_minexp}) is finer than the "
+                         f"stream's (maxprec {maxprec}, minexp {minexp}); widening is not supported, the planes a "
+                         "finer mode codes are not in the stream")
+    if size_only and out is not None:
+        raise ValueError("truncate_variable: size_only writes no stream; give no out")
+    if not words.is_cuda or not lengths.is_cuda:
+        raise ValueError("truncate_variable: expects a device stream and a device index")
+    if lengths.element_size() != 2 or not lengths.is_contiguous() or not words.is_contiguous():
+        raise ValueError("truncate_variable: lengths must be a contiguous 16-bit tensor, words contiguous")
+    shape = tuple(int(s) for s in shape)
+    nx, ny, nz = _extents(shape)
+    nblocks = _block_count(shape)
+    if lengths.numel() != nblocks:
+        raise ValueError(f"truncate_variable: lengths has {lengths.numel()} entries, the array has {nblocks} blocks")
+    n = library().cuzfp_hip_truncate_variable_workspace_bytes(t, nx, ny, nz)
+    if n == 0:
+        raise CodecError("truncate_variable", 1)
+    s = stream if stream is not None else torch.cuda.current_stream(words.device)
+    with torch.cuda.stream(s):
+        ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=words.device)
+        if out is None and not size_only:
+            out = torch.empty(variable_maximum_size(shape, dtype, new_maxprec) // 8, dtype=torch.int64,
+                              device=words.device)
+        new_lengths = torch.empty(nblocks, dtype=torch.int16, device=words.device)
+        total = torch.empty(1, dtype=torch.int64, device=words.device)
+    if out is not None and (not out.is_cuda or not out.is_contiguous() or out.element_size() != 8):
+        raise ValueError("truncate_variable: out must be a contiguous device tensor of 64-bit words")
+    rc = library().cuzfp_hip_truncate_variable(words.data_ptr(), words.numel() * words.element_size(),
+                                               lengths.data_ptr(), t, nx, ny, nz, maxprec, minexp, new_maxprec,
+                                               new_minexp, out.data_ptr() if out is not None else None,
+                                               out.numel() * 8 if out is not None else 0, new_lengths.data_ptr(),
+                                               total.data_ptr(), ws.data_ptr(), n, _stream_handle(stream))
+    _check("truncate_variable", rc)
+    with torch.cuda.stream(s):
+        nbits = int(total.item())  # the one synchronisation: the count is data dependent
+    if out is None:
+        return None, new_lengths, nbits
+    return out[: min((nbits + 63) // 64, out.numel())], new_lengths, nbits
 
 
 def copy(src, dst, stream=None):

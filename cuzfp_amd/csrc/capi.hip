@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "launch.hpp"
+#include "rerate_variable.hpp"
 #include "variable_index.hpp"
 
 namespace cuzfp {
@@ -1072,6 +1073,53 @@ int cuzfp_hip_decode_region_variable(const uint64_t* d_stream, size_t stream_byt
                                                      stream);
   return launch_decode_region_variable_type<double>(p, r, d_stream, stream_bytes, d_lengths, d_index, fast, d_out,
                                                     stream);
+}
+
+// ---------------------------------------------------------------------------
+// A variable-rate stream cut to a coarser mode (truncate_variable.hip)
+
+// both streams' offsets and the scan's tile sums
+static size_t truncate_variable_workspace_of(const Geometry& g) {
+  return 8 * (2 * (size_t)g.nblocks + variable_tiles(g.nblocks));
+}
+
+size_t cuzfp_hip_truncate_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz) {
+  Problem p;
+  if (make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p) != CUZFP_SUCCESS) return 0;
+  return truncate_variable_workspace_of(p.g);
+}
+
+int cuzfp_hip_truncate_variable(const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                int type, unsigned nx, unsigned ny, unsigned nz,
+                                unsigned maxprec, int minexp, unsigned new_maxprec, int new_minexp,
+                                uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths,
+                                uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                                hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
+  if (rc) return rc;
+  const unsigned prec = type == CUZFP_TYPE_FLOAT ? 32 : 64;
+  if (maxprec < 1 || maxprec > prec || new_maxprec < 1 || new_maxprec > prec) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // no widening: the planes a finer mode would add are not in the stream (cuzfp_hip.h)
+  if (!variable_mode_coarsens(maxprec, minexp, new_maxprec, new_minexp)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_src || !d_src_lengths || !d_lengths || !d_total_bits || !d_workspace) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_dst && dst_capacity) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_src & 3) || (((uintptr_t)d_src_lengths | (uintptr_t)d_lengths) & 1) ||
+      (((uintptr_t)d_dst | (uintptr_t)d_total_bits | (uintptr_t)d_workspace) & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (workspace_bytes < truncate_variable_workspace_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the copy pass reads source bits other lanes' stores would overwrite, and
+  // the lengths pass reads source lengths beside the ones it writes
+  const uintptr_t s0 = (uintptr_t)d_src, t0 = (uintptr_t)d_dst;
+  if (d_dst && s0 < t0 + dst_capacity && t0 < s0 + src_bytes) return CUZFP_ERROR_INVALID_ARGUMENT;
+  const uintptr_t l0 = (uintptr_t)d_src_lengths, m0 = (uintptr_t)d_lengths, lbytes = 2 * (uintptr_t)p.g.nblocks;
+  if (l0 < m0 + lbytes && m0 < l0 + lbytes) return CUZFP_ERROR_INVALID_ARGUMENT;
+  uint64_t* src_offsets = (uint64_t*)d_workspace;
+  uint64_t* offsets = src_offsets + p.g.nblocks;
+  uint64_t* partials = offsets + p.g.nblocks;
+  return launch_truncate_variable(type == CUZFP_TYPE_DOUBLE, p.dims, d_src, src_bytes, d_src_lengths, p.g.nblocks,
+                                  new_maxprec, new_minexp, d_dst, dst_capacity / 8, d_lengths, d_total_bits,
+                                  src_offsets, offsets, partials, stream);
 }
 
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {

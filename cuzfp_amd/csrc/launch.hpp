@@ -138,6 +138,17 @@ int launch_decode_variable_type(const Problem& p, const uint64_t* stream, size_t
                                 const uint16_t* lengths, bool fast, void* out, uint64_t* offsets,
                                 uint64_t* partials, hipStream_t st);
 
+// cuzfp_hip_truncate_variable (truncate_variable.hip, rerate_variable.hpp):
+// the stream `src` with the index `src_lengths` cut to the mode (new_maxprec,
+// new_minexp): lengths, *total, and `dst` below cap_words (cap_words == 0:
+// lengths and *total only).  src_offsets and offsets hold nblocks words each,
+// partials variable_tiles(nblocks).  No load outside [src, src + src_bytes)
+// and src_lengths[0 .. nblocks) whatever src_lengths holds.
+int launch_truncate_variable(bool is_double, unsigned dims, const uint64_t* src, size_t src_bytes,
+                             const uint16_t* src_lengths, uint32_t nblocks, uint32_t new_maxprec, int new_minexp,
+                             uint64_t* dst, uint64_t cap_words, uint16_t* lengths, uint64_t* total,
+                             uint64_t* src_offsets, uint64_t* offsets, uint64_t* partials, hipStream_t st);
+
 // The offset index of a variable-rate stream and the sub-box decoder that reads
 // it (variable_index.hpp, region_variable_kernels.hpp).
 //   index: index[t] = the bit offset of block 64 t, index[T] = the total; the

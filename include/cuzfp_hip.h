@@ -340,6 +340,57 @@ int cuzfp_hip_decode_region_variable(const uint64_t* d_stream, size_t stream_byt
                                      unsigned ex, unsigned ey, unsigned ez,
                                      long long sx, long long sy, long long sz, void* d_out, hipStream_t stream);
 
+/* Not reference entry points (callers test CUZFP_HIP_HAS_VARIABLE_TRUNCATE):
+ * coarsen a variable-rate stream without recoding -- cuzfp_hip_truncate's
+ * counterpart for the variable-rate modes.
+ *
+ * The rule.  A stream written at the mode (maxprec, minexp) can be cut to
+ * (new_maxprec, new_minexp) when new_maxprec <= maxprec and new_minexp >=
+ * minexp (anything else is widening and is refused); precision and accuracy
+ * modes mix freely under it, e.g. a full-precision stream (maxprec 32 / 64,
+ * minexp -1074) can be cut to any tolerance.  The coder is embedded, so every
+ * block of the coarser stream is then the first bits of the finer stream's
+ * block, up to the end of the planes the coarser mode codes for the block's
+ * exponent -- with one exception: a block the coarser mode codes no plane of
+ * becomes the one-bit form, the single bit 0, while the finer block starts
+ * with a 1.  The result is byte for byte the stream, and the lengths, CPU zfp
+ * 0.5.0 writes for the original array at (new_maxprec, new_minexp).  Nothing
+ * is decoded: a block's new length is found by walking its bit-plane code,
+ * and its prefix is copied.
+ *
+ * cuzfp_hip_truncate_variable_workspace_bytes: bytes of device scratch the
+ *   call needs (both streams' 64-bit block offsets and the scan's partial
+ *   sums), 8-byte aligned; 0 for invalid dimensions and integer types.
+ * cuzfp_hip_truncate_variable: asynchronous on `stream`, no allocation, no
+ *   synchronisation (two three-launch scans, the lengths pass, a zero fill,
+ *   the copy pass).  Writes d_lengths[0 .. nblocks), the 64-bit bit count
+ *   *d_total_bits, and the new stream's ceil(total / 64) words with zero pad
+ *   bits in the last, no byte past them and none at or past dst_capacity: if
+ *   the stream does not fit, the lengths and the count are still right and
+ *   d_dst's contents are unspecified.  No new length exceeds its block's
+ *   source length, so src_bytes always fit.  d_dst == NULL with dst_capacity
+ *   == 0 is the size query: lengths and count only.  The source index is not
+ *   trusted, by cuzfp_hip_decode_variable's rule: a length is clamped to the
+ *   type's longest block, one no coded block can have reads as a zero block,
+ *   and whatever d_src_lengths holds, nothing outside [d_src, d_src +
+ *   src_bytes) and d_src_lengths[0 .. nblocks) is read and nothing outside the
+ *   outputs is written; blocks whose entries are wrong give unspecified bits.
+ *   Before any launch: CUZFP_ERROR_UNSUPPORTED_TYPE for integer types;
+ *   CUZFP_ERROR_INVALID_ARGUMENT for widening, maxprec or new_maxprec outside
+ *   1 .. the type's precision, a null or misaligned pointer (d_src 4 bytes,
+ *   the lengths 2, d_dst, d_total_bits and the workspace 8), a workspace below
+ *   cuzfp_hip_truncate_variable_workspace_bytes, [d_src, d_src + src_bytes)
+ *   overlapping [d_dst, d_dst + dst_capacity), and d_lengths overlapping
+ *   d_src_lengths. */
+#define CUZFP_HIP_HAS_VARIABLE_TRUNCATE 1
+size_t cuzfp_hip_truncate_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz);
+int cuzfp_hip_truncate_variable(const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                int type, unsigned nx, unsigned ny, unsigned nz,
+                                unsigned maxprec, int minexp, unsigned new_maxprec, int new_minexp,
+                                uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths,
+                                uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                                hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,
