@@ -105,6 +105,9 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_decode_region_variable.argtypes = [vp, sz, vp, vp, sz, i, u, u, u, u, u, u, u, u, u, ll, ll, ll,
                                                      vp, vp]
     lib.cuzfp_hip_truncate_variable_workspace_bytes.restype = sz
+    lib.cuzfp_hip_decode_region_variable_coarse.restype = i
+    lib.cuzfp_hip_decode_region_variable_coarse.argtypes = [vp, sz, vp, vp, sz, i, u, u, u, u, i, u, u, u, u, u, u,
+                                                            ll, ll, ll, vp, vp]
     lib.cuzfp_hip_truncate_variable_workspace_bytes.argtypes = [i, u, u, u]
     lib.cuzfp_hip_truncate_variable.restype = i
     lib.cuzfp_hip_truncate_variable.argtypes = [vp, sz, vp, i, u, u, u, u, i, u, i, vp, sz, vp, vp, vp, sz, vp]
@@ -478,7 +481,8 @@ def encode_variable(x, precision=None, tolerance=None, out=None, stream=None):
     return out[: min((nbits + 63) // 64, out.numel())], lengths, nbits
 
 
-def decode_variable(words, lengths, shape, dtype, out=None, stream=None, index=None):
+def decode_variable(words, lengths, shape, dtype, out=None, stream=None, index=None, precision=None,
+                    tolerance=None):
     """Decompress a variable-rate device stream (`words`, 64-bit words) with its
     block index `lengths` (int16 tensor of raw uint16 bits, from
     `encode_variable`) into a new (or given, possibly strided) CUDA tensor:
@@ -490,8 +494,23 @@ def decode_variable(words, lengths, shape, dtype, out=None, stream=None, index=N
 
     `index` (from `variable_index`) decodes through `decode_region_variable`
     with the whole array as the box: one launch, no scan of the lengths and no
-    workspace.  None scans the lengths on every call."""
+    workspace.  None scans the lengths on every call.
+
+    One of `precision` and `tolerance` decodes the array at that coarser target
+    mode straight from the stream, never finer than the stream holds it: the
+    semantics of `decode_region_variable`'s keywords, whose path this takes
+    with the whole array as the box.  With `index` that is one launch; with
+    ``index=None`` the index is built for the call by `variable_index` (a scan
+    of the lengths and its scratch) first.  `truncate_variable` gives the
+    coarser *stream*."""
     import torch
+    if precision is not None or tolerance is not None:
+        shape = tuple(int(s) for s in (shape if out is None else out.shape))
+        _coarse_target("decode_variable", dtype if out is None else out.dtype, precision, tolerance)
+        if index is None:
+            index = variable_index(lengths, shape, dtype if out is None else out.dtype, stream=stream)
+        return decode_region_variable(words, lengths, index, shape, dtype, (0,) * len(shape), shape, out=out,
+                                      stream=stream, precision=precision, tolerance=tolerance)
     if index is not None:
         shape = tuple(int(s) for s in (shape if out is None else out.shape))
         return decode_region_variable(words, lengths, index, shape, dtype, (0,) * len(shape), shape, out=out,
@@ -564,7 +583,19 @@ def variable_index(lengths, shape, dtype, out=None, stream=None):
     return out[: n // 8]
 
 
-def decode_region_variable(words, lengths, index, shape, dtype, origin, extent, out=None, stream=None):
+def _coarse_target(where, dtype, precision, tolerance):
+    """(maxprec, minexp) of the target of a coarse decode: exactly one of
+    `precision` and `tolerance`, checked before anything touches a device."""
+    if precision is not None and tolerance is not None:
+        raise ValueError(f"{where}: give at most one of precision and tolerance")
+    t = type_code(dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError(where, 2)
+    return _variable_mode(where, 32 if t == TYPE_FLOAT else 64, precision, tolerance, ("precision", "tolerance"))
+
+
+def decode_region_variable(words, lengths, index, shape, dtype, origin, extent, out=None, stream=None,
+                           precision=None, tolerance=None):
     """Decompress the box ``origin .. origin + extent`` (slowest first, like
     `shape`) of the array a variable-rate device stream holds into a new (or
     given, possibly strided) CUDA tensor of shape `extent`: bit for bit the box
@@ -574,8 +605,29 @@ def decode_region_variable(words, lengths, index, shape, dtype, origin, extent, 
     allocation when `out` is given, no synchronisation (it can be captured into
     a graph).  Neither `index` nor `lengths` can make the decoder read outside
     `words` or write outside the box; blocks whose entries are wrong decode to
-    unspecified values."""
+    unspecified values.
+
+    One of `precision` (bit planes a block, 1 .. 32 / 64) and `tolerance` names
+    a target mode coarser than the one that wrote the stream, and the box is
+    decoded at it straight from the fine stream, still in one launch with no
+    scratch: every lane walks its block's bit-plane code to the block's length
+    at the target and decodes that prefix, or zeros where the target codes no
+    plane of the block.  With a mode as the pair (maxprec, minexp) --
+    precision p: (p, -1074); tolerance t: (the type's 32 / 64,
+    accuracy_to_minexp(t)) -- and a target that coarsens the stream's mode,
+    the result is bit for bit `decode_variable` of `truncate_variable`'s
+    output, which is what CPU zfp 0.5.0 decodes from its own stream at the
+    target mode.  The call does not take the mode that wrote the stream and
+    refuses no target: a block never decodes finer than the stream holds it,
+    so the result is the array at (the smaller maxprec, the larger minexp),
+    and a target at or above the stream's own mode gives the plain decode.
+    Widening is not offered in the sense that nothing finer comes out.
+    `truncate_variable` is the way to get the coarser *stream*.  Both None is
+    the plain decode; both given is a ValueError."""
     import torch
+    target = None
+    if precision is not None or tolerance is not None:
+        target = _coarse_target("decode_region_variable", dtype if out is None else out.dtype, precision, tolerance)
     shape = tuple(int(s) for s in shape)
     origin = tuple(int(o) for o in origin)
     extent = tuple(int(e) for e in extent)
@@ -607,6 +659,13 @@ def decode_region_variable(words, lengths, index, shape, dtype, origin, extent, 
     ox, oy, oz = _extents(origin)
     ex, ey, ez = _extents(extent)
     sx, sy, sz = _strides(out)
+    if target is not None:
+        rc = library().cuzfp_hip_decode_region_variable_coarse(
+            words.data_ptr(), words.numel() * words.element_size(), lengths.data_ptr(), index.data_ptr(),
+            index.numel() * index.element_size(), t, nx, ny, nz, target[0], target[1], ox, oy, oz, ex, ey, ez,
+            sx, sy, sz, out.data_ptr(), _stream_handle(stream))
+        _check("decode_region_variable", rc)
+        return out
     rc = library().cuzfp_hip_decode_region_variable(words.data_ptr(), words.numel() * words.element_size(),
                                                     lengths.data_ptr(), index.data_ptr(),
                                                     index.numel() * index.element_size(), t, nx, ny, nz,

@@ -1039,15 +1039,19 @@ int cuzfp_hip_variable_index(const uint16_t* d_lengths, int type, unsigned nx, u
   return launch_variable_index(d_lengths, p.g.nblocks, d_index, offsets, offsets + p.g.nblocks, stream);
 }
 
-int cuzfp_hip_decode_region_variable(const uint64_t* d_stream, size_t stream_bytes, const uint16_t* d_lengths,
-                                     const uint64_t* d_index, size_t index_bytes, int type,
-                                     unsigned nx, unsigned ny, unsigned nz,
-                                     unsigned ox, unsigned oy, unsigned oz,
-                                     unsigned ex, unsigned ey, unsigned ez,
-                                     long long sx, long long sy, long long sz, void* d_out, hipStream_t stream) {
+// cuzfp_hip_decode_region_variable (coarse false: maxprec and minexp unused) and
+// cuzfp_hip_decode_region_variable_coarse: one set of checks, in one order
+static int decode_region_variable_impl(const uint64_t* d_stream, size_t stream_bytes, const uint16_t* d_lengths,
+                                       const uint64_t* d_index, size_t index_bytes, int type,
+                                       unsigned nx, unsigned ny, unsigned nz, bool coarse, unsigned maxprec,
+                                       int minexp, unsigned ox, unsigned oy, unsigned oz,
+                                       unsigned ex, unsigned ey, unsigned ez,
+                                       long long sx, long long sy, long long sz, void* d_out, hipStream_t stream) {
   Problem p;
   int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
   if (rc) return rc;
+  // the target mode, as cuzfp_hip_truncate_variable checks its new mode
+  if (coarse && (maxprec < 1 || maxprec > (type == CUZFP_TYPE_FLOAT ? 32u : 64u))) return CUZFP_ERROR_INVALID_ARGUMENT;
   if (!d_out || !d_stream || !d_lengths || !d_index) return CUZFP_ERROR_INVALID_ARGUMENT;
   if (((uintptr_t)d_stream & 3) || ((uintptr_t)d_lengths & 1) || ((uintptr_t)d_index & 7))
     return CUZFP_ERROR_INVALID_ARGUMENT;
@@ -1068,11 +1072,41 @@ int cuzfp_hip_decode_region_variable(const uint64_t* d_stream, size_t stream_byt
   const bool fast = !((ox | ex) & 3) && (p.dims < 2 || !((oy | ey) & 3)) && (p.dims < 3 || !((oz | ez) & 3)) &&
                     r.sx == 1 && r.sy == (long long)ex && r.sz == (long long)ex * ey &&
                     ((uintptr_t)d_out & 15) == 0;
+  if (coarse) {
+    if (type == CUZFP_TYPE_FLOAT)
+      return launch_decode_region_variable_coarse_type<float>(p, r, d_stream, stream_bytes, d_lengths, d_index,
+                                                              maxprec, minexp, fast, d_out, stream);
+    return launch_decode_region_variable_coarse_type<double>(p, r, d_stream, stream_bytes, d_lengths, d_index,
+                                                             maxprec, minexp, fast, d_out, stream);
+  }
   if (type == CUZFP_TYPE_FLOAT)
     return launch_decode_region_variable_type<float>(p, r, d_stream, stream_bytes, d_lengths, d_index, fast, d_out,
                                                      stream);
   return launch_decode_region_variable_type<double>(p, r, d_stream, stream_bytes, d_lengths, d_index, fast, d_out,
                                                     stream);
+}
+
+int cuzfp_hip_decode_region_variable(const uint64_t* d_stream, size_t stream_bytes, const uint16_t* d_lengths,
+                                     const uint64_t* d_index, size_t index_bytes, int type,
+                                     unsigned nx, unsigned ny, unsigned nz,
+                                     unsigned ox, unsigned oy, unsigned oz,
+                                     unsigned ex, unsigned ey, unsigned ez,
+                                     long long sx, long long sy, long long sz, void* d_out, hipStream_t stream) {
+  return decode_region_variable_impl(d_stream, stream_bytes, d_lengths, d_index, index_bytes, type, nx, ny, nz, false,
+                                     0, 0, ox, oy, oz, ex, ey, ez, sx, sy, sz, d_out, stream);
+}
+
+// The same box at a coarser target mode, straight from the fine stream
+// (variable_coarse.hpp, region_variable_coarse_kernels.hpp)
+int cuzfp_hip_decode_region_variable_coarse(const uint64_t* d_stream, size_t stream_bytes, const uint16_t* d_lengths,
+                                            const uint64_t* d_index, size_t index_bytes, int type,
+                                            unsigned nx, unsigned ny, unsigned nz, unsigned maxprec, int minexp,
+                                            unsigned ox, unsigned oy, unsigned oz,
+                                            unsigned ex, unsigned ey, unsigned ez,
+                                            long long sx, long long sy, long long sz, void* d_out,
+                                            hipStream_t stream) {
+  return decode_region_variable_impl(d_stream, stream_bytes, d_lengths, d_index, index_bytes, type, nx, ny, nz, true,
+                                     maxprec, minexp, ox, oy, oz, ex, ey, ez, sx, sy, sz, d_out, stream);
 }
 
 // ---------------------------------------------------------------------------

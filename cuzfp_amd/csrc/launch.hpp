@@ -164,4 +164,13 @@ int launch_decode_region_variable_type(const Problem& p, const Region& r, const 
                                        const uint16_t* lengths, const uint64_t* index, bool fast, void* out,
                                        hipStream_t st);
 
+// cuzfp_hip_decode_region_variable_coarse (variable_coarse.hpp,
+// region_variable_coarse_kernels.hpp): launch_decode_region_variable_type with
+// every block decoded at the target mode (maxprec 1 .. the type's precision,
+// minexp), never finer than the stream holds it; one launch, the same bounds.
+template <typename Scalar>
+int launch_decode_region_variable_coarse_type(const Problem& p, const Region& r, const uint64_t* stream,
+                                              size_t stream_bytes, const uint16_t* lengths, const uint64_t* index,
+                                              uint32_t maxprec, int minexp, bool fast, void* out, hipStream_t st);
+
 }  // namespace cuzfp

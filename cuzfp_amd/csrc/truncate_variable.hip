@@ -23,25 +23,9 @@
 // hold whatever the source index holds.
 #include "kernels.hpp"
 #include "rerate_variable.hpp"
+#include "source_window.hpp"  // SourceWindow: 64 bits of the source from a block's first bit on
 
 namespace cuzfp {
-
-// 64 bits of the source from a block's first bit on; dwords at or past the
-// stream's end read as zero
-struct SourceWindow {
-  const uint32_t* __restrict__ base;
-  uint64_t dwords;
-  uint64_t off;
-  __device__ __forceinline__ uint64_t window(uint32_t pos) const {
-    const uint64_t bit = off + pos;
-    const uint64_t d = bit >> 5;
-    const uint32_t s = (uint32_t)bit & 31u;
-    const uint32_t a0 = d < dwords ? base[d] : 0u;
-    const uint32_t a1 = d + 1 < dwords ? base[d + 1] : 0u;
-    const uint32_t a2 = d + 2 < dwords ? base[d + 2] : 0u;
-    return (uint64_t)__builtin_amdgcn_alignbit(a1, a0, s) | ((uint64_t)__builtin_amdgcn_alignbit(a2, a1, s) << 32);
-  }
-};
 
 // Lengths pass: one lane, one block.  The walk diverges by lane (its trip count
 // is the block's own); the loads around it are per lane and bounded.

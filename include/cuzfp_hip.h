@@ -391,6 +391,55 @@ int cuzfp_hip_truncate_variable(const uint64_t* d_src, size_t src_bytes, const u
                                 uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
                                 hipStream_t stream);
 
+/* Not a reference entry point (callers test
+ * CUZFP_HIP_HAS_VARIABLE_DECODE_COARSE): decode a sub-box of a variable-rate
+ * stream at a coarser precision or tolerance straight from the fine stream --
+ * what cuzfp_hip_decode_region_prefix is to cuzfp_hip_truncate, for the
+ * variable-rate modes.  cuzfp_hip_truncate_variable makes the coarser *stream*;
+ * this call makes no stream, no lengths and no index, and its work is
+ * proportional to the box.
+ *
+ * The target mode is (maxprec, minexp): precision p is (p, -1074), tolerance t
+ * is (the type's 32 / 64, cuzfp_hip_accuracy_to_minexp(t)).  Every block of the
+ * box is decoded from the first L' of its bits, L' its length at the target
+ * mode, found by walking its bit-plane code as cuzfp_hip_truncate_variable
+ * does; a block the target codes no plane of decodes to zeros.  Where the
+ * target coarsens the mode that wrote the stream (cuzfp_hip_truncate_variable's
+ * rule), the box is bit for bit the box of cuzfp_hip_decode_variable on
+ * cuzfp_hip_truncate_variable's output, and of what CPU zfp 0.5.0's
+ * zfp_decompress returns for its own stream at the target mode.
+ *
+ * Never finer than the stream.  The call does not take the mode that wrote the
+ * stream, and refuses no target for being finer: the walk ends at the block's
+ * own length, so a block decodes from at most the bits the stream holds of it.
+ * The result is the array at (the smaller of the two maxprec, the larger of
+ * the two minexp); a target at or above the stream's mode gives
+ * cuzfp_hip_decode_region_variable's bytes.  Nothing finer than the stream
+ * comes out: widening is still not offered.
+ *
+ * One kernel launch, no workspace, no allocation, no synchronisation; it can be
+ * captured into a graph.  The arguments other than the target are
+ * cuzfp_hip_decode_region_variable's, with its checks in its order and its
+ * status codes; maxprec outside 1 .. the type's precision is
+ * CUZFP_ERROR_INVALID_ARGUMENT, integer types CUZFP_ERROR_UNSUPPORTED_TYPE,
+ * all before any launch.  Neither the stream, the index nor the lengths are
+ * trusted: whatever they hold, nothing outside [d_stream, d_stream +
+ * stream_bytes), d_lengths[0 .. nblocks) and d_index[0 .. T) is read and
+ * nothing outside the box is written.  The kernel's block image is sized for
+ * the longest block a mode with `maxprec` planes writes; a block whose bits
+ * walk further than that (arbitrary bits, entries of another stream) is
+ * decoded from that many bits and, like any block whose entries are wrong,
+ * gives unspecified values. */
+#define CUZFP_HIP_HAS_VARIABLE_DECODE_COARSE 1
+int cuzfp_hip_decode_region_variable_coarse(const uint64_t* d_stream, size_t stream_bytes,
+                                            const uint16_t* d_lengths, const uint64_t* d_index, size_t index_bytes,
+                                            int type, unsigned nx, unsigned ny, unsigned nz,
+                                            unsigned maxprec, int minexp,
+                                            unsigned ox, unsigned oy, unsigned oz,
+                                            unsigned ex, unsigned ey, unsigned ez,
+                                            long long sx, long long sy, long long sz, void* d_out,
+                                            hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,
