@@ -22,7 +22,7 @@ __all__ = [
     "library", "library_path", "rate_to_maxbits", "stream_bytes", "maximum_size",
     "encode", "decode", "decode_region", "encode_region", "truncate", "compress_host", "decompress_host", "type_code",
     "encode_variable", "decode_variable", "accuracy_to_minexp", "variable_maximum_size",
-    "variable_index", "decode_region_variable", "truncate_variable",
+    "variable_index", "decode_region_variable", "truncate_variable", "encode_region_variable",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -111,6 +111,13 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_truncate_variable_workspace_bytes.argtypes = [i, u, u, u]
     lib.cuzfp_hip_truncate_variable.restype = i
     lib.cuzfp_hip_truncate_variable.argtypes = [vp, sz, vp, i, u, u, u, u, i, u, i, vp, sz, vp, vp, vp, sz, vp]
+    lib.cuzfp_hip_encode_region_variable_workspace_bytes.restype = sz
+    lib.cuzfp_hip_encode_region_variable_workspace_bytes.argtypes = [i, u, u, u]
+    lib.cuzfp_hip_encode_region_variable_maximum_size.restype = sz
+    lib.cuzfp_hip_encode_region_variable_maximum_size.argtypes = [i, u, u, u, sz, u, u, u, u, u, u, u]
+    lib.cuzfp_hip_encode_region_variable.restype = i
+    lib.cuzfp_hip_encode_region_variable.argtypes = [vp, ll, ll, ll, i, u, u, u, u, i, u, u, u, u, u, u,
+                                                     vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -767,6 +774,113 @@ def truncate_variable(words, lengths, shape, dtype, *, from_precision=None, from
     if out is None:
         return None, new_lengths, nbits
     return out[: min((nbits + 63) // 64, out.numel())], new_lengths, nbits
+
+
+def encode_region_variable(x, words, lengths, index, shape, origin, *, precision=None, tolerance=None,
+                           out=None, stream=None, with_index=False):
+    """Write the box `x` (a device float tensor whose shape is the box's extent)
+    at `origin` (slowest first, like `shape`) into the array a variable-rate
+    device stream holds; returns ``(words, lengths, nbits)`` of the updated
+    array like `encode_variable`, or ``(words, lengths, nbits, index)`` with
+    ``with_index=True``.  `words`, `lengths` and `index` (`variable_index` of
+    `lengths`) are the source and are not changed: block lengths change, so the
+    update is out of place.
+
+    Exactly one of `precision` and `tolerance` names the mode the touched
+    blocks are coded at.  With A = ``decode_variable(words, lengths)``, M = A
+    with the box replaced by `x` and E = ``encode_variable(M, mode)``: a block
+    the box touches is E's block with E's length, every other block is its
+    source bits and length, unchanged, and the blocks are packed back to back
+    as `encode_variable` packs them.  A touched block the box covers (all its
+    elements inside the array lie in the box) is coded from `x` alone.  A
+    partly covered block is a read-modify-write: it is decoded from its old
+    bits, the box's elements are replaced and it is coded again, so its other
+    elements are re-coded from their decoded values.  If the box is a union of
+    covered blocks and `x` the new array's values there, the result is byte
+    for byte `encode_variable` of the new array -- what CPU zfp 0.5.0 writes.
+
+    The mode applies to the touched blocks only and may differ from the mode
+    that wrote the rest: a brick of interest can be kept at ``precision=32``
+    inside a ``tolerance=1e-2`` archive.  The decoders need only the block
+    boundaries and take such a stream as it is; `truncate_variable` assumes one
+    mode for the whole stream.
+
+    `x` may be strided; a broadcast view (fill the box with a constant) is
+    materialised on the launch stream as `encode_region` does.  `out` (64-bit
+    words, not overlapping `words`) is allocated at the call's own worst case
+    when None -- the source's bits plus the longest block of the mode for every
+    touched block, proportional to the stream and the box rather than the
+    array; a shorter `out` is never written past its end, but then holds no
+    valid stream if nbits exceeds it.  The new `lengths` is a new int16 tensor;
+    ``with_index=True`` also returns the new offset index, equal to
+    `variable_index` of the new lengths and written by the pass that places
+    the blocks, at no extra launch.  An index that does not belong to the
+    stream cannot make the call read outside `words`, `lengths` and `index` or
+    write outside its outputs.  Asynchronous on `stream` except for one
+    synchronisation to read the count, as `encode_variable`."""
+    import torch
+    t = type_code(x.dtype)
+    # (the mode is checked first, against the precision of the box's element size)
+    maxprec, minexp = _variable_mode("encode_region_variable", 32 if t in (TYPE_INT32, TYPE_FLOAT) else 64,
+                                     precision, tolerance, ("precision", "tolerance"))
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError("encode_region_variable", 2)
+    shape = tuple(int(s) for s in shape)
+    origin = tuple(int(o) for o in origin)
+    extent = tuple(int(e) for e in getattr(x, "shape", ()))
+    nx, ny, nz = _extents(shape)
+    if len(origin) != len(shape) or len(extent) != len(shape):
+        raise ValueError(f"encode_region_variable: origin {origin} and the box's shape {extent} must have "
+                         f"the rank of shape {shape}")
+    if any(o < 0 for o in origin) or any(e <= 0 for e in extent):
+        raise ValueError("encode_region_variable: origin must be non-negative and the box not empty")
+    if any(o + e > n for o, e, n in zip(origin, extent, shape)):
+        raise ValueError(f"encode_region_variable: the box {origin} + {extent} leaves the array {shape}")
+    if not x.is_cuda or not words.is_cuda or not lengths.is_cuda or not index.is_cuda:
+        raise ValueError("encode_region_variable: expects a device box, a device stream and device indices")
+    if lengths.element_size() != 2 or not lengths.is_contiguous() or not words.is_contiguous():
+        raise ValueError("encode_region_variable: lengths must be a contiguous 16-bit tensor, words contiguous")
+    if index.element_size() != 8 or not index.is_contiguous():
+        raise ValueError("encode_region_variable: index must be a contiguous tensor of 64-bit words")
+    nblocks = _block_count(shape)
+    if lengths.numel() != nblocks:
+        raise ValueError(f"encode_region_variable: lengths has {lengths.numel()} entries, the array has "
+                         f"{nblocks} blocks")
+    lib = library()
+    n = lib.cuzfp_hip_encode_region_variable_workspace_bytes(t, nx, ny, nz)
+    if n == 0:
+        raise CodecError("encode_region_variable", 1)
+    x = _materialise(x, stream)
+    ox, oy, oz = _extents(origin)
+    ex, ey, ez = _extents(extent)
+    sx, sy, sz = _strides(x)
+    src_bytes = words.numel() * words.element_size()
+    s = stream if stream is not None else torch.cuda.current_stream(words.device)
+    with torch.cuda.stream(s):
+        ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=words.device)
+        if out is None:
+            cap = lib.cuzfp_hip_encode_region_variable_maximum_size(t, nx, ny, nz, src_bytes, ex, ey, ez, ox, oy, oz,
+                                                                    maxprec)
+            if cap == 0:
+                raise CodecError("encode_region_variable", 1)
+            out = torch.empty(cap // 8, dtype=torch.int64, device=words.device)
+        new_lengths = torch.empty(nblocks, dtype=torch.int16, device=words.device)
+        new_index = torch.empty(index.numel(), dtype=torch.int64, device=words.device) if with_index else None
+        total = torch.empty(1, dtype=torch.int64, device=words.device)
+    if not out.is_cuda or not out.is_contiguous() or out.element_size() != 8:
+        raise ValueError("encode_region_variable: out must be a contiguous device tensor of 64-bit words")
+    rc = lib.cuzfp_hip_encode_region_variable(
+        x.data_ptr(), sx, sy, sz, t, nx, ny, nz, maxprec, minexp, ox, oy, oz, ex, ey, ez,
+        words.data_ptr(), src_bytes, lengths.data_ptr(), index.data_ptr(), index.numel() * index.element_size(),
+        out.data_ptr(), out.numel() * 8, new_lengths.data_ptr(),
+        new_index.data_ptr() if with_index else None, total.data_ptr(), ws.data_ptr(), n, _stream_handle(stream))
+    _check("encode_region_variable", rc)
+    with torch.cuda.stream(s):
+        nbits = int(total.item())  # the one synchronisation: the count is data dependent
+    new_words = out[: min((nbits + 63) // 64, out.numel())]
+    if with_index:
+        return new_words, new_lengths, nbits, new_index[: (nblocks + 63) // 64 + 1]
+    return new_words, new_lengths, nbits
 
 
 def copy(src, dst, stream=None):

@@ -1156,6 +1156,101 @@ int cuzfp_hip_truncate_variable(const uint64_t* d_src, size_t src_bytes, const u
                                   src_offsets, offsets, partials, stream);
 }
 
+// ---------------------------------------------------------------------------
+// A sub-box of a variable-rate stream coded anew, out of place
+// (region_variable_update_kernels.hpp)
+
+// the most bits a block takes at maxprec (cuzfp_hip_variable_maximum_size's)
+static unsigned variable_block_bits(int type, unsigned dims, unsigned maxprec) {
+  const unsigned values = 1u << (2 * dims);
+  return std::min(min_bits(type) + values - 1 + values * maxprec, 4171u);
+}
+
+size_t cuzfp_hip_encode_region_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz) {
+  Problem p;
+  if (make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p) != CUZFP_SUCCESS) return 0;
+  return variable_workspace_of(p.g);
+}
+
+size_t cuzfp_hip_encode_region_variable_maximum_size(int type, unsigned nx, unsigned ny, unsigned nz, size_t src_bytes,
+                                                     unsigned ex, unsigned ey, unsigned ez,
+                                                     unsigned ox, unsigned oy, unsigned oz, unsigned maxprec) {
+  Problem p;
+  if (make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p) != CUZFP_SUCCESS) return 0;
+  if (maxprec < 1 || maxprec > (type == CUZFP_TYPE_FLOAT ? 32u : 64u)) return 0;
+  if (p.dims < 2 && (oy || ey)) return 0;
+  if (p.dims < 3 && (oz || ez)) return 0;
+  if (p.dims < 2) ey = 1;
+  if (p.dims < 3) ez = 1;
+  if (!ex || !ey || !ez) return 0;
+  if (ox >= p.g.nx || ex > p.g.nx - ox || oy >= p.g.ny || ey > p.g.ny - oy || oz >= p.g.nz || ez > p.g.nz - oz)
+    return 0;
+  if (src_bytes > ((size_t)1 << 60)) return 0;  // 8 * src_bytes must not wrap
+  const Region r = make_region(p.g, ox, oy, oz, ex, ey, ez, 0, 0, 0);
+  // every replaced block gives back at least one bit of the source's
+  const size_t bits = 8 * src_bytes + (size_t)r.nrb * variable_block_bits(type, p.dims, maxprec);
+  return 8 * ((bits + 63) / 64);
+}
+
+int cuzfp_hip_encode_region_variable(const void* d_box, long long sx, long long sy, long long sz, int type,
+                                     unsigned nx, unsigned ny, unsigned nz, unsigned maxprec, int minexp,
+                                     unsigned ox, unsigned oy, unsigned oz,
+                                     unsigned ex, unsigned ey, unsigned ez,
+                                     const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                     const uint64_t* d_src_index, size_t index_bytes,
+                                     uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths, uint64_t* d_index,
+                                     uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                                     hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
+  if (rc) return rc;
+  if (maxprec < 1 || maxprec > (type == CUZFP_TYPE_FLOAT ? 32u : 64u)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_box || !d_src || !d_src_lengths || !d_src_index || !d_lengths || !d_total_bits || !d_workspace)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_dst && dst_capacity) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_src & 3) || (((uintptr_t)d_src_lengths | (uintptr_t)d_lengths) & 1) ||
+      (((uintptr_t)d_src_index | (uintptr_t)d_dst | (uintptr_t)d_index | (uintptr_t)d_total_bits |
+        (uintptr_t)d_workspace) & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the box rules of cuzfp_hip_decode_region
+  if (p.dims < 2 && (oy || ey)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 3 && (oz || ez)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 2) ey = 1;
+  if (p.dims < 3) ez = 1;
+  if (!ex || !ey || !ez) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ox >= p.g.nx || ex > p.g.nx - ox || oy >= p.g.ny || ey > p.g.ny - oy || oz >= p.g.nz ||
+      ez > p.g.nz - oz)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the index of the source, and of the result when one is asked for
+  if (index_bytes < variable_index_bytes_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (workspace_bytes < variable_workspace_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the copy pass and the merge read source bits, lengths and index entries
+  // beside the ones other lanes write
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+  };
+  const size_t lbytes = 2 * (size_t)p.g.nblocks, ibytes = variable_index_bytes_of(p.g);
+  if (overlap(d_src, src_bytes, d_dst, dst_capacity)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (overlap(d_src_lengths, lbytes, d_lengths, lbytes)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (overlap(d_src_index, ibytes, d_index, ibytes)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  const Region r = make_region(p.g, ox, oy, oz, ex, ey, ez, sx, sy, sz);
+  const bool covered = region_covered(p.g, r);
+  // a contiguous, 16-byte aligned box of whole blocks: the row loads
+  const bool rows = covered && !(ex & 3) && (p.dims < 2 || !(ey & 3)) && (p.dims < 3 || !(ez & 3)) &&
+                    r.sx == 1 && r.sy == (long long)ex && r.sz == (long long)ex * ey &&
+                    ((uintptr_t)d_box & 15) == 0;
+  uint64_t* offsets = (uint64_t*)d_workspace;
+  uint64_t* partials = offsets + p.g.nblocks;
+  if (type == CUZFP_TYPE_FLOAT)
+    return launch_encode_region_variable_type<float>(p, r, d_box, covered, rows, maxprec, minexp, d_src, src_bytes,
+                                                     d_src_lengths, d_src_index, d_dst, dst_capacity / 8, d_lengths,
+                                                     d_index, d_total_bits, offsets, partials, stream);
+  return launch_encode_region_variable_type<double>(p, r, d_box, covered, rows, maxprec, minexp, d_src, src_bytes,
+                                                    d_src_lengths, d_src_index, d_dst, dst_capacity / 8, d_lengths,
+                                                    d_index, d_total_bits, offsets, partials, stream);
+}
+
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {
   if (!d_src || !d_dst || (bytes & 15) || (((uintptr_t)d_src | (uintptr_t)d_dst) & 15))
     return CUZFP_ERROR_INVALID_ARGUMENT;

@@ -173,4 +173,19 @@ int launch_decode_region_variable_coarse_type(const Problem& p, const Region& r,
                                               size_t stream_bytes, const uint16_t* lengths, const uint64_t* index,
                                               uint32_t maxprec, int minexp, bool fast, void* out, hipStream_t st);
 
+// cuzfp_hip_encode_region_variable (region_variable_update_kernels.hpp): the
+// stream `src` with `src_lengths` and `src_index`, the blocks the box touches
+// coded anew from `box` at (maxprec, minexp) and every other block copied:
+// lengths, *total, the new index unless dst_index is null, and `dst` below
+// cap_words.  covered and rows as launch_encode_region_type; offsets holds
+// nblocks words, partials variable_tiles(nblocks).  No load outside [src, src +
+// src_bytes), src_lengths[0 .. nblocks) and src_index[0 .. T) whatever the two
+// hold.
+template <typename Scalar>
+int launch_encode_region_variable_type(const Problem& p, const Region& r, const void* box, bool covered, bool rows,
+                                       uint32_t maxprec, int minexp, const uint64_t* src, size_t src_bytes,
+                                       const uint16_t* src_lengths, const uint64_t* src_index, uint64_t* dst,
+                                       uint64_t cap_words, uint16_t* lengths, uint64_t* dst_index, uint64_t* total,
+                                       uint64_t* offsets, uint64_t* partials, hipStream_t st);
+
 }  // namespace cuzfp

@@ -440,6 +440,79 @@ int cuzfp_hip_decode_region_variable_coarse(const uint64_t* d_stream, size_t str
                                             long long sx, long long sy, long long sz, void* d_out,
                                             hipStream_t stream);
 
+/* Not reference entry points (callers test
+ * CUZFP_HIP_HAS_ENCODE_REGION_VARIABLE): write new values for a sub-box into a
+ * variable-rate stream -- cuzfp_hip_encode_region's counterpart for the
+ * variable-rate modes.  Block lengths change, so the update is out of place:
+ * the call reads the stream, its lengths and its offset index and writes the
+ * stream, the lengths, the bit count and (optionally) the index of the updated
+ * array.
+ *
+ * With A the array the source decodes to, M = A with the box replaced by d_box,
+ * and E the stream cuzfp_hip_encode_variable writes for M at (maxprec, minexp):
+ * a block the box touches is E's block, with E's length; any other block is
+ * its bits of the source, unchanged, with its source length; the blocks lie
+ * back to back in raster order and the pad to the next 64-bit word is zero
+ * (the layout of cuzfp_hip_encode_variable and cuzfp_hip_truncate_variable).
+ * A touched block all of whose elements inside the array lie in the box is
+ * coded from d_box alone; any other touched block is decoded from its old
+ * bits, the box's elements are replaced, elements outside the array are padded
+ * by the encoder's rule, and it is coded again -- its other elements are thus
+ * re-coded from decoded values, as in cuzfp_hip_encode_region.  A box that is
+ * a union of covered blocks, filled with the new array's values, gives byte
+ * for byte cuzfp_hip_encode_variable of the new array.  (maxprec, minexp)
+ * applies to the touched blocks only and need not be the mode that wrote the
+ * rest: the decoders need block boundaries, not the mode.
+ *
+ * cuzfp_hip_encode_region_variable_workspace_bytes: device scratch of the call
+ *   (the new 64-bit block offsets and the scan's partial sums), 8-byte aligned;
+ *   0 for invalid dimensions and integer types.
+ * cuzfp_hip_encode_region_variable_maximum_size: 8 * ceil((8 * src_bytes +
+ *   touched_blocks * B) / 64) bytes, B the most bits a block takes at maxprec
+ *   (cuzfp_hip_variable_maximum_size's): a true bound on the result, every
+ *   replaced block giving back at least one bit, proportional to the stream
+ *   and the box, not to the array.  0 for an invalid argument.
+ * cuzfp_hip_encode_region_variable: asynchronous on `stream`, no allocation, no
+ *   synchronisation (a copy of the lengths, the lengths pass over the touched
+ *   blocks, a three-launch scan, a zero fill, the copy pass over all blocks,
+ *   the encode pass over the touched blocks).  d_box is the box's element
+ *   (0, 0, 0), sx, sy, sz its element strides (0: contiguous).  d_src_index is
+ *   cuzfp_hip_variable_index of d_src_lengths, index_bytes its size.  Writes
+ *   d_lengths[0 .. nblocks), *d_total_bits, the result's ceil(total / 64)
+ *   words, no byte past them and none at or past dst_capacity (if the stream
+ *   does not fit, the lengths, the count and the index are still right and
+ *   d_dst's contents are unspecified), and, unless d_index is NULL, the
+ *   result's offset index there (index_bytes: the two indices have one size),
+ *   equal to cuzfp_hip_variable_index of d_lengths.  The source index and
+ *   lengths are not trusted, by the decoders' rule: whatever they hold, nothing
+ *   outside [d_src, d_src + src_bytes), d_src_lengths[0 .. nblocks) and
+ *   d_src_index[0 .. T) is read and nothing outside the outputs is written;
+ *   blocks whose entries are wrong give unspecified bits (the lengths of the
+ *   covered blocks are still those of E).
+ *   Before any launch: CUZFP_ERROR_UNSUPPORTED_TYPE for integer and unknown
+ *   types; CUZFP_ERROR_INVALID_ARGUMENT for invalid dimensions, maxprec outside
+ *   1 .. the type's precision, a null pointer (d_index and, with dst_capacity
+ *   0, d_dst excepted), a misaligned one (d_src 4 bytes, the lengths 2, the
+ *   indices, d_dst, d_total_bits and the workspace 8), the box errors of
+ *   cuzfp_hip_decode_region, index_bytes below cuzfp_hip_variable_index_bytes,
+ *   a workspace below cuzfp_hip_encode_region_variable_workspace_bytes, [d_src,
+ *   d_src + src_bytes) overlapping [d_dst, d_dst + dst_capacity), d_lengths
+ *   overlapping d_src_lengths, and d_index overlapping d_src_index. */
+#define CUZFP_HIP_HAS_ENCODE_REGION_VARIABLE 1
+size_t cuzfp_hip_encode_region_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz);
+size_t cuzfp_hip_encode_region_variable_maximum_size(int type, unsigned nx, unsigned ny, unsigned nz,
+                                                     size_t src_bytes, unsigned ex, unsigned ey, unsigned ez,
+                                                     unsigned ox, unsigned oy, unsigned oz, unsigned maxprec);
+int cuzfp_hip_encode_region_variable(const void* d_box, long long sx, long long sy, long long sz, int type,
+                                     unsigned nx, unsigned ny, unsigned nz, unsigned maxprec, int minexp,
+                                     unsigned ox, unsigned oy, unsigned oz,
+                                     unsigned ex, unsigned ey, unsigned ez,
+                                     const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                     const uint64_t* d_src_index, size_t index_bytes,
+                                     uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths, uint64_t* d_index,
+                                     uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                                     hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,
