@@ -57,6 +57,7 @@ __device__ __forceinline__ void stamp_real(int slot) {
 
 #include "zfp_block.hpp"
 #include "launch.hpp"
+#include "wave_index.hpp"
 
 namespace cuzfp {
 
@@ -702,6 +703,22 @@ constexpr int kWavesPerGroup = 4;
 #define CUZFP_DEC_WPG 4
 #endif
 constexpr int kEncWaves = CUZFP_ENC_WPG, kDecWaves = CUZFP_DEC_WPG;
+// The 3D decoder in one resident round of waves (256^3 at rate 8: 4,096 waves,
+// 16 on each of 256 CUs): 16-wave workgroups, one a CU, so the 16 KiB of chunk
+// tables are copied once a CU rather than four times (16 MiB -> 4 MiB of
+// L2-to-LDS traffic a launch), each taking the waves of the four encoder
+// workgroups that ran on its own XCD (decode_wave_of's remap, wave_index.hpp:
+// with consecutive waves a larger workgroup reads segments other XCDs wrote).
+// 256^3 r8, interleaved (tools/xvar.py, profiles/r07_ab_groups.txt): decode
+// 23.9 -> 23.1 us, step 45.69 -> 45.45 us polynomial, 44.80 -> 43.76 us
+// splitmix; 8-wave groups the same on polynomial and 0.9 us behind on
+// splitmix, 8 without the remap 0.2 and 1.0 us behind.  Not beyond one round:
+// 1024^3 r8 decode 1,265 -> 1,319 us with 8-wave groups and 1,531 us with 16.
+// 0 = off.
+#ifndef CUZFP_DEC_WPG_ROUND  // A/B builds
+#define CUZFP_DEC_WPG_ROUND 16
+#endif
+constexpr int kDecWavesRound = CUZFP_DEC_WPG_ROUND;
 // Workgroup size of the 1D register-reader decoder: 16 waves, so that the
 // workgroup's 20 KiB of tables are shared by 16 waves that each decode 1 KiB
 // of values (64M values: decode 151 -> 121 us).  The 2D decoder and the 1D/2D
@@ -1052,7 +1069,13 @@ __device__ __forceinline__ void zfp_decode_body(const uint64_t* __restrict__ str
   extern __shared__ __attribute__((aligned(16))) uint64_t lds_all[];
   constexpr int N = 1 << (2 * DIMS);
   const uint32_t wig = wave_in_group();
-  const uint32_t wave = g.wave0 + bid * (blockDim.x >> 6) + wig;
+  // (3D LDS-image kernels: a workgroup larger than the encoder's takes the
+  // waves of the encoder workgroups that ran on its own XCD, decode_wave_of)
+  uint32_t wave;
+  if constexpr (DIMS == 3 && !REG)
+    wave = g.wave0 + decode_wave_of(bid, wig, blockDim.x >> 6, kEncWaves, g.xcd_remap != 0);
+  else
+    wave = g.wave0 + bid * (blockDim.x >> 6) + wig;
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t b = wave * kLanes + lane;
   const bool live = wave < g.wave_end && b < g.nblocks;
@@ -1435,12 +1458,8 @@ static inline uint32_t waves_per_group(uint32_t lds_words, size_t shared_bytes, 
 // 768^3 by 14 % of the step.  CUZFP_PRIO=0/1 in the environment forces either.
 // The environment is read once per process (a function-local static: thread-safe
 // initialisation); the CU count once per device, as lds_cap_bytes.
-static inline bool use_priority(uint32_t nwaves, int waves_per_simd, uint32_t rounds) {
-  static const int forced = [] {
-    const char* e = getenv("CUZFP_PRIO");
-    return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1;
-  }();
-  if (forced >= 0) return forced != 0;
+// (within_rounds: the launch is at most `rounds` resident rounds of waves)
+static inline bool within_rounds(uint32_t nwaves, int waves_per_simd, uint32_t rounds) {
   static std::atomic<int> cus[kMaxDevices];
   int dev = 0, c = 256;  // MI355X
   if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices) {
@@ -1453,6 +1472,14 @@ static inline bool use_priority(uint32_t nwaves, int waves_per_simd, uint32_t ro
     }
   }
   return nwaves <= (uint32_t)c * 4u * (uint32_t)waves_per_simd * rounds;
+}
+static inline bool use_priority(uint32_t nwaves, int waves_per_simd, uint32_t rounds) {
+  static const int forced = [] {
+    const char* e = getenv("CUZFP_PRIO");
+    return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1;
+  }();
+  if (forced >= 0) return forced != 0;
+  return within_rounds(nwaves, waves_per_simd, rounds);
 }
 
 #if defined(CUZFP_XVAR)  // tools/xvar.py builds: the fast-gather kernels only (compile time)
@@ -1608,6 +1635,34 @@ int launch_decode_t(const uint64_t* stream, const Geometry& g, bool fast, void* 
   // double (two waves a SIMD) up to one: at 256^3 r16 (two rounds) its decode
   // measured 56.6 -> 54.9 us without it (r04_f64prio)
   constexpr uint32_t kDecPrioRounds = (sizeof(Scalar) == 8 && DIMS == 3) ? 1 : 2;
+  // One resident round of 3D waves: kDecWavesRound-wave workgroups on the
+  // encoder's XCDs (see kDecWavesRound) -- where the wave count allows the
+  // remap (without it the larger workgroups measured slower than today's),
+  // every image and the tables fit one workgroup's LDS, the encoder's
+  // workgroups are kEncWaves waves, and the schedule is on (it is, in one
+  // round, unless CUZFP_PRIO=0: one kernel the fewer to build).  32-bit
+  // values only: the double decoder's 189 VGPRs hold two waves a SIMD, eight
+  // a CU.
+  if constexpr (DIMS == 3 && sizeof(Scalar) == 4 && kDecWavesRound > kDecWaves) {
+    constexpr uint32_t R = kDecWavesRound;
+    if (within_rounds(nwaves, occupancy<Scalar, DIMS>::value, 1) && decode_remap_ok(nwaves, R, kEncWaves) &&
+        (size_t)R * gg.lds_words * 8 + kStatic <= lds_cap_bytes() &&
+        waves_per_group(g.maxbits + kLanes * kSlackWords, kSpreadTabBytes + 16, kEncWaves) == (uint32_t)kEncWaves &&
+        use_priority(nwaves, occupancy<Scalar, DIMS>::value, kDecPrioRounds)) {
+      gg.xcd_remap = 1;
+      const dim3 rgrid(nwaves / R), rblock(kLanes * R);
+      const size_t rlds = (size_t)R * gg.lds_words * 8;
+      if (fast)
+        hipLaunchKernelGGL((zfp_decode<Scalar, DIMS, true, true, 0, R>), rgrid, rblock, rlds, st, stream, gg, d);
+      else if constexpr (!kFastOnly)
+        hipLaunchKernelGGL((zfp_decode<Scalar, DIMS, false, true, 0, R>), rgrid, rblock, rlds, st, stream, gg, d);
+      else
+        return CUZFP_ERROR_UNSUPPORTED_TYPE;
+      const hipError_t e = hipGetLastError();
+      t_last_hip = e;
+      return e == hipSuccess ? CUZFP_SUCCESS : CUZFP_ERROR_HIP;
+    }
+  }
   if (fast && !use_priority(nwaves, occupancy<Scalar, DIMS>::value, kDecPrioRounds))
     hipLaunchKernelGGL((zfp_decode<Scalar, DIMS, true, false>), grid, block, lds, st, stream, gg, d);
   else if (fast)

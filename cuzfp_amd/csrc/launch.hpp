@@ -29,6 +29,9 @@ struct Geometry {
   // 3D double decoder: rows a pass when its row stores are staged through the
   // wave's LDS image (0: stored straight from the lanes), see kernels.hpp
   uint32_t row_stage;
+  // 3D LDS-image decoder: workgroups take their waves by decode_wave_of's
+  // remap (wave_index.hpp) rather than consecutively
+  uint32_t xcd_remap;
 };
 
 // q = floor(n / d) = (n * m) >> s for every n < 2^31, with s = 31 + ceil(log2 d)

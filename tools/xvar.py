@@ -36,11 +36,9 @@ def _stub_objs(unit):
     os.makedirs(STUB, exist_ok=True)
     hdrs = [os.path.join(b.CSRC, h) for h in b.HEADERS] + [os.path.join(b.INC, "cuzfp_hip.h")]
     objs, procs = [], []
-    for u, flags in (("inst_f32", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("inst_f64", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]),
-                     ("inst_i32", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]), ("inst_i64", ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"]),
-                     ("region_f32", []), ("region_f64", []), ("region_i32", []), ("region_i64", []),
-                     ("update_f32", []), ("update_f64", []), ("update_i32", []), ("update_i64", []), ("truncate", []),
-                     ("capi", [])):
+    # (every other unit of the product library as it is: the C-ABI refers to them all)
+    for u in b.KERNEL_UNITS:
+        flags = ["-DCUZFP_XVAR", "-DCUZFP_XVAR_STUB"] if u.startswith("inst_") else []
         if u == unit:
             continue
         o = os.path.join(STUB, u + ".o")
