@@ -23,6 +23,7 @@ __all__ = [
     "encode", "decode", "decode_region", "encode_region", "truncate", "compress_host", "decompress_host", "type_code",
     "encode_variable", "decode_variable", "accuracy_to_minexp", "variable_maximum_size",
     "variable_index", "decode_region_variable", "truncate_variable", "encode_region_variable",
+    "extract_region_variable", "insert_region_variable",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -118,6 +119,20 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_encode_region_variable.restype = i
     lib.cuzfp_hip_encode_region_variable.argtypes = [vp, ll, ll, ll, i, u, u, u, u, i, u, u, u, u, u, u,
                                                      vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]
+    lib.cuzfp_hip_extract_region_variable_workspace_bytes.restype = sz
+    lib.cuzfp_hip_extract_region_variable_workspace_bytes.argtypes = [i, u, u, u]
+    lib.cuzfp_hip_extract_region_variable_maximum_size.restype = sz
+    lib.cuzfp_hip_extract_region_variable_maximum_size.argtypes = [i, u, u, u, sz, u, u, u, u, u, u]
+    lib.cuzfp_hip_extract_region_variable.restype = i
+    lib.cuzfp_hip_extract_region_variable.argtypes = [vp, sz, vp, vp, sz, i, u, u, u, u, u, u, u, u, u,
+                                                      vp, sz, vp, vp, sz, vp, vp, sz, vp]
+    lib.cuzfp_hip_insert_region_variable_workspace_bytes.restype = sz
+    lib.cuzfp_hip_insert_region_variable_workspace_bytes.argtypes = [i, u, u, u]
+    lib.cuzfp_hip_insert_region_variable_maximum_size.restype = sz
+    lib.cuzfp_hip_insert_region_variable_maximum_size.argtypes = [sz, sz]
+    lib.cuzfp_hip_insert_region_variable.restype = i
+    lib.cuzfp_hip_insert_region_variable.argtypes = [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, i, u, u, u,
+                                                     u, u, u, u, u, u, vp, sz, vp, vp, vp, vp, sz, vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -880,6 +895,189 @@ def encode_region_variable(x, words, lengths, index, shape, origin, *, precision
     new_words = out[: min((nbits + 63) // 64, out.numel())]
     if with_index:
         return new_words, new_lengths, nbits, new_index[: (nblocks + 63) // 64 + 1]
+    return new_words, new_lengths, nbits
+
+
+def _aligned_box(where, shape, dtype, origin, extent):
+    """(type code, shape, origin, extent) of a crop or paste, checked before
+    anything touches a device: the dtype, the rank, the box inside the array,
+    and the alignment."""
+    t = type_code(dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError(where, 2)
+    shape = tuple(int(s) for s in shape)
+    origin = tuple(int(o) for o in origin)
+    extent = tuple(int(e) for e in extent)
+    _extents(shape)
+    if len(origin) != len(shape) or len(extent) != len(shape):
+        raise ValueError(f"{where}: origin {origin} and extent {extent} must have the rank of shape {shape}")
+    if any(o < 0 for o in origin) or any(e <= 0 for e in extent):
+        raise ValueError(f"{where}: origin must be non-negative and the box not empty")
+    if any(o + e > n for o, e, n in zip(origin, extent, shape)):
+        raise ValueError(f"{where}: the box {origin} + {extent} leaves the array {shape}")
+    if any(o % 4 or (e % 4 and o + e != n) for o, e, n in zip(origin, extent, shape)):
+        raise ValueError(f"{where}: the box {origin} + {extent} is not block-aligned in the array {shape} (on every "
+                         "axis the origin must be a multiple of 4 and the extent one too, or reach the array's end); "
+                         "decode_region_variable / encode_region_variable handle partial coverage, by decoding")
+    return t, shape, origin, extent
+
+
+def _check_variable_stream(where, what, words, lengths, index, nblocks):
+    """A stream, its lengths and its index as the crop and paste calls take them."""
+    if not words.is_cuda or not lengths.is_cuda or not index.is_cuda:
+        raise ValueError(f"{where}: expects a device {what} stream and device indices")
+    if lengths.element_size() != 2 or not lengths.is_contiguous() or not words.is_contiguous():
+        raise ValueError(f"{where}: {what} lengths must be a contiguous 16-bit tensor, words contiguous")
+    if index.element_size() != 8 or not index.is_contiguous():
+        raise ValueError(f"{where}: {what} index must be a contiguous tensor of 64-bit words")
+    if lengths.numel() != nblocks:
+        raise ValueError(f"{where}: {what} lengths has {lengths.numel()} entries, the {what} has {nblocks} blocks")
+
+
+def extract_region_variable(words, lengths, index, shape, dtype, origin, extent, *, out=None, stream=None,
+                            with_index=False):
+    """Crop the block-aligned box ``origin .. origin + extent`` (slowest first,
+    like `shape`) out of a variable-rate device stream without decoding it;
+    returns ``(words, lengths, nbits)`` of a stand-alone stream of an array of
+    shape `extent`, like `encode_variable`, or ``(words, lengths, nbits,
+    index)`` with ``with_index=True``.  `index` is `variable_index` of
+    `lengths`; the source is not changed.
+
+    zfp codes every block on its own, so the box's blocks, copied bit for bit
+    and packed back to back in the box's raster order, are byte for byte what
+    `encode_variable` -- and CPU zfp 0.5.0 -- writes for the sub-array at the
+    mode that wrote the source.  Nothing is decoded or coded again, and no mode
+    is needed.  The result feeds `decode_variable`, `variable_index`,
+    `decode_region_variable`, `truncate_variable` and `insert_region_variable`
+    unchanged.
+
+    The box must be aligned: on every axis the origin a multiple of 4, and the
+    extent a multiple of 4 or reaching the array's end.  Any other box is a
+    ValueError; `decode_region_variable` decodes such a box.
+
+    `out` (64-bit words, not overlapping `words`) is allocated at the call's
+    worst case when None -- the lesser of the source's bits and the type's
+    longest block for every block of the box; a shorter `out` is never written
+    past its end, but then holds no valid stream if nbits exceeds it.  An index
+    that does not belong to the stream cannot make the call read outside
+    `words`, `lengths` and `index` or write outside its outputs.  Asynchronous
+    on `stream` except for one synchronisation to read the count, as
+    `encode_variable`."""
+    import torch
+    where = "extract_region_variable"
+    t, shape, origin, extent = _aligned_box(where, shape, dtype, origin, extent)
+    _check_variable_stream(where, "source", words, lengths, index, _block_count(shape))
+    nx, ny, nz = _extents(shape)
+    ox, oy, oz = _extents(origin)
+    ex, ey, ez = _extents(extent)
+    lib = library()
+    n = lib.cuzfp_hip_extract_region_variable_workspace_bytes(t, ex, ey, ez)
+    if n == 0:
+        raise CodecError(where, 1)
+    nrb = _block_count(extent)
+    src_bytes = words.numel() * words.element_size()
+    s = stream if stream is not None else torch.cuda.current_stream(words.device)
+    with torch.cuda.stream(s):
+        ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=words.device)
+        if out is None:
+            cap = lib.cuzfp_hip_extract_region_variable_maximum_size(t, nx, ny, nz, src_bytes, ex, ey, ez, ox, oy, oz)
+            if cap == 0:
+                raise CodecError(where, 1)
+            out = torch.empty(cap // 8, dtype=torch.int64, device=words.device)
+        new_lengths = torch.empty(nrb, dtype=torch.int16, device=words.device)
+        new_index = torch.empty((nrb + 63) // 64 + 1, dtype=torch.int64, device=words.device) if with_index else None
+        total = torch.empty(1, dtype=torch.int64, device=words.device)
+    if not out.is_cuda or not out.is_contiguous() or out.element_size() != 8:
+        raise ValueError(f"{where}: out must be a contiguous device tensor of 64-bit words")
+    rc = lib.cuzfp_hip_extract_region_variable(
+        words.data_ptr(), src_bytes, lengths.data_ptr(), index.data_ptr(), index.numel() * index.element_size(),
+        t, nx, ny, nz, ox, oy, oz, ex, ey, ez, out.data_ptr() if out.numel() else None, out.numel() * 8,
+        new_lengths.data_ptr(), new_index.data_ptr() if with_index else None,
+        new_index.numel() * 8 if with_index else 0, total.data_ptr(), ws.data_ptr(), n, _stream_handle(stream))
+    _check(where, rc)
+    with torch.cuda.stream(s):
+        nbits = int(total.item())  # the one synchronisation: the count is data dependent
+    new_words = out[: min((nbits + 63) // 64, out.numel())]
+    if with_index:
+        return new_words, new_lengths, nbits, new_index
+    return new_words, new_lengths, nbits
+
+
+def insert_region_variable(box_words, box_lengths, box_index, words, lengths, index, shape, dtype, origin, extent, *,
+                           out=None, stream=None, with_index=False):
+    """Paste the variable-rate device stream of a brick (`box_words`,
+    `box_lengths`, `box_index`: a stream of an array of shape `extent`) over
+    the block-aligned box ``origin .. origin + extent`` of the array another
+    stream (`words`, `lengths`, `index`) holds, without decoding either;
+    returns ``(words, lengths, nbits)`` of the updated array like
+    `encode_variable`, or ``(words, lengths, nbits, index)`` with
+    ``with_index=True``.  Each index is `variable_index` of its lengths.
+    Neither input is changed: block lengths change, so the call is out of
+    place, like `encode_region_variable`.
+
+    A block inside the box is the brick's block, with the brick's length; every
+    other block is its source bits and length; all are packed back to back as
+    `encode_variable` packs them.  Pasting ``encode_variable(X, mode)`` gives
+    what ``encode_region_variable(X, ..., origin, mode)`` gives on the same
+    box, and what `extract_region_variable` cropped goes back byte for byte.
+
+    The brick must be of the archive's dtype and rank -- the caller states that
+    and the call cannot check it -- and `box_lengths` must have one entry for
+    every block of the box.  The call knows no modes: a ``precision=32`` brick
+    may go into a ``tolerance=1e-2`` archive, by the argument of
+    `encode_region_variable`: the decoders need the block boundaries, not the
+    mode.  The box must be aligned, as for `extract_region_variable`;
+    `encode_region_variable` writes any other box, from values.
+
+    Assembling an array from its slabs: the stream of an all-zero array is one
+    0 bit a block -- ``nblocks`` lengths of 1, ceil(nblocks / 64) zero words --
+    and pasting each slab's stream into it, slab by slab, gives the stream of
+    the whole array.
+
+    `out` (64-bit words, overlapping neither input) is allocated at the bits of
+    both inputs when None; a shorter `out` is never written past its end, but
+    then holds no valid stream if nbits exceeds it.  Indices and lengths that do
+    not belong to their streams cannot make the call read outside its inputs or
+    write outside its outputs.  Asynchronous on `stream` except for one
+    synchronisation to read the count, as `encode_variable`."""
+    import torch
+    where = "insert_region_variable"
+    t, shape, origin, extent = _aligned_box(where, shape, dtype, origin, extent)
+    nblocks = _block_count(shape)
+    _check_variable_stream(where, "source", words, lengths, index, nblocks)
+    _check_variable_stream(where, "box", box_words, box_lengths, box_index, _block_count(extent))
+    nx, ny, nz = _extents(shape)
+    ox, oy, oz = _extents(origin)
+    ex, ey, ez = _extents(extent)
+    lib = library()
+    n = lib.cuzfp_hip_insert_region_variable_workspace_bytes(t, nx, ny, nz)
+    if n == 0:
+        raise CodecError(where, 1)
+    src_bytes = words.numel() * words.element_size()
+    box_bytes = box_words.numel() * box_words.element_size()
+    s = stream if stream is not None else torch.cuda.current_stream(words.device)
+    with torch.cuda.stream(s):
+        ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=words.device)
+        if out is None:
+            cap = lib.cuzfp_hip_insert_region_variable_maximum_size(src_bytes, box_bytes)
+            out = torch.empty(cap // 8, dtype=torch.int64, device=words.device)
+        new_lengths = torch.empty(nblocks, dtype=torch.int16, device=words.device)
+        new_index = torch.empty((nblocks + 63) // 64 + 1, dtype=torch.int64, device=words.device) if with_index else None
+        total = torch.empty(1, dtype=torch.int64, device=words.device)
+    if not out.is_cuda or not out.is_contiguous() or out.element_size() != 8:
+        raise ValueError(f"{where}: out must be a contiguous device tensor of 64-bit words")
+    rc = lib.cuzfp_hip_insert_region_variable(
+        box_words.data_ptr(), box_bytes, box_lengths.data_ptr(), box_index.data_ptr(),
+        box_index.numel() * box_index.element_size(), words.data_ptr(), src_bytes, lengths.data_ptr(),
+        index.data_ptr(), index.numel() * index.element_size(), t, nx, ny, nz, ox, oy, oz, ex, ey, ez,
+        out.data_ptr() if out.numel() else None, out.numel() * 8, new_lengths.data_ptr(),
+        new_index.data_ptr() if with_index else None, total.data_ptr(), ws.data_ptr(), n, _stream_handle(stream))
+    _check(where, rc)
+    with torch.cuda.stream(s):
+        nbits = int(total.item())  # the one synchronisation: the count is data dependent
+    new_words = out[: min((nbits + 63) // 64, out.numel())]
+    if with_index:
+        return new_words, new_lengths, nbits, new_index
     return new_words, new_lengths, nbits
 
 

@@ -1252,6 +1252,154 @@ int cuzfp_hip_encode_region_variable(const void* d_box, long long sx, long long 
                                                     d_index, d_total_bits, offsets, partials, stream);
 }
 
+// ---------------------------------------------------------------------------
+// Crop and paste of a block-aligned box of a variable-rate stream
+// (region_variable_crop_kernels.hpp)
+
+// The box rules of cuzfp_hip_decode_region (ey and ez normalised to 1 along an
+// unused dimension), then the alignment both calls ask for: region_covered.
+static int make_aligned_region(const Problem& p, unsigned ox, unsigned oy, unsigned oz, unsigned ex, unsigned ey,
+                               unsigned ez, Region* r) {
+  if (p.dims < 2 && (oy || ey)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 3 && (oz || ez)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (p.dims < 2) ey = 1;
+  if (p.dims < 3) ez = 1;
+  if (!ex || !ey || !ez) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ox >= p.g.nx || ex > p.g.nx - ox || oy >= p.g.ny || ey > p.g.ny - oy || oz >= p.g.nz || ez > p.g.nz - oz)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  *r = make_region(p.g, ox, oy, oz, ex, ey, ez, 0, 0, 0);
+  return region_covered(p.g, *r) ? CUZFP_SUCCESS : CUZFP_ERROR_INVALID_ARGUMENT;
+}
+
+// the longest block of the type (variable_longest_block)
+static unsigned variable_longest_of(int type, unsigned dims) {
+  return variable_block_bits(type, dims, type == CUZFP_TYPE_FLOAT ? 32 : 64);
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// the workspace and the index of an array of the box's extent
+size_t cuzfp_hip_extract_region_variable_workspace_bytes(int type, unsigned ex, unsigned ey, unsigned ez) {
+  return cuzfp_hip_variable_workspace_bytes(type, ex, ey, ez);
+}
+
+size_t cuzfp_hip_extract_region_variable_maximum_size(int type, unsigned nx, unsigned ny, unsigned nz,
+                                                      size_t src_bytes, unsigned ex, unsigned ey, unsigned ez,
+                                                      unsigned ox, unsigned oy, unsigned oz) {
+  Problem p;
+  Region r;
+  if (make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p) != CUZFP_SUCCESS) return 0;
+  if (make_aligned_region(p, ox, oy, oz, ex, ey, ez, &r) != CUZFP_SUCCESS) return 0;
+  if (src_bytes > ((size_t)1 << 60)) return 0;  // 8 * src_bytes must not wrap
+  // no block is longer than the type's longest, and all of them are bits of the source
+  const size_t bits = std::min(8 * src_bytes, (size_t)r.nrb * variable_longest_of(type, p.dims));
+  return 8 * ((bits + 63) / 64);
+}
+
+int cuzfp_hip_extract_region_variable(const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                      const uint64_t* d_src_index, size_t index_bytes, int type,
+                                      unsigned nx, unsigned ny, unsigned nz,
+                                      unsigned ox, unsigned oy, unsigned oz,
+                                      unsigned ex, unsigned ey, unsigned ez,
+                                      uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths,
+                                      uint64_t* d_index, size_t dst_index_bytes, uint64_t* d_total_bits,
+                                      void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
+  if (rc) return rc;
+  if (!d_src || !d_src_lengths || !d_src_index || !d_lengths || !d_total_bits || !d_workspace)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_dst && dst_capacity) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_src & 3) || (((uintptr_t)d_src_lengths | (uintptr_t)d_lengths) & 1) ||
+      (((uintptr_t)d_src_index | (uintptr_t)d_dst | (uintptr_t)d_index | (uintptr_t)d_total_bits |
+        (uintptr_t)d_workspace) & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  Region r;
+  rc = make_aligned_region(p, ox, oy, oz, ex, ey, ez, &r);
+  if (rc) return rc;
+  // the index of the source; the box's own index and workspace are those of an array of r.nrb blocks
+  const size_t box_ibytes = 8 * ((size_t)variable_index_tiles(r.nrb) + 1);
+  if (index_bytes < variable_index_bytes_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (d_index && dst_index_bytes < box_ibytes) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (workspace_bytes < 8 * ((size_t)r.nrb + variable_tiles(r.nrb))) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the copy pass reads source bits, lengths and index entries beside the ones other lanes write
+  if (ranges_overlap(d_src, src_bytes, d_dst, dst_capacity)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ranges_overlap(d_src_lengths, 2 * (size_t)p.g.nblocks, d_lengths, 2 * (size_t)r.nrb))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ranges_overlap(d_src_index, variable_index_bytes_of(p.g), d_index, box_ibytes))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  uint64_t* offsets = (uint64_t*)d_workspace;
+  uint64_t* partials = offsets + r.nrb;
+  if (type == CUZFP_TYPE_FLOAT)
+    return launch_extract_region_variable_type<float>(p.dims, r, d_src, src_bytes, d_src_lengths, d_src_index, d_dst,
+                                                      dst_capacity / 8, d_lengths, d_index, d_total_bits, offsets,
+                                                      partials, stream);
+  return launch_extract_region_variable_type<double>(p.dims, r, d_src, src_bytes, d_src_lengths, d_src_index, d_dst,
+                                                     dst_capacity / 8, d_lengths, d_index, d_total_bits, offsets,
+                                                     partials, stream);
+}
+
+size_t cuzfp_hip_insert_region_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz) {
+  return cuzfp_hip_variable_workspace_bytes(type, nx, ny, nz);
+}
+
+size_t cuzfp_hip_insert_region_variable_maximum_size(size_t src_bytes, size_t box_bytes) {
+  if (src_bytes > ((size_t)1 << 59) || box_bytes > ((size_t)1 << 59)) return 0;  // the sum of the bits must not wrap
+  return 8 * ((8 * src_bytes + 8 * box_bytes + 63) / 64);
+}
+
+int cuzfp_hip_insert_region_variable(const uint64_t* d_box, size_t box_bytes, const uint16_t* d_box_lengths,
+                                     const uint64_t* d_box_index, size_t box_index_bytes,
+                                     const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                     const uint64_t* d_src_index, size_t index_bytes, int type,
+                                     unsigned nx, unsigned ny, unsigned nz,
+                                     unsigned ox, unsigned oy, unsigned oz,
+                                     unsigned ex, unsigned ey, unsigned ez,
+                                     uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths, uint64_t* d_index,
+                                     uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                                     hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
+  if (rc) return rc;
+  if (!d_box || !d_box_lengths || !d_box_index || !d_src || !d_src_lengths || !d_src_index || !d_lengths ||
+      !d_total_bits || !d_workspace)
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_dst && dst_capacity) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if ((((uintptr_t)d_box | (uintptr_t)d_src) & 3) ||
+      (((uintptr_t)d_box_lengths | (uintptr_t)d_src_lengths | (uintptr_t)d_lengths) & 1) ||
+      (((uintptr_t)d_box_index | (uintptr_t)d_src_index | (uintptr_t)d_dst | (uintptr_t)d_index |
+        (uintptr_t)d_total_bits | (uintptr_t)d_workspace) & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  Region r;
+  rc = make_aligned_region(p, ox, oy, oz, ex, ey, ez, &r);
+  if (rc) return rc;
+  // the index of the box's stream, and of the source and of the result (one size)
+  const size_t box_ibytes = 8 * ((size_t)variable_index_tiles(r.nrb) + 1), ibytes = variable_index_bytes_of(p.g);
+  if (box_index_bytes < box_ibytes || index_bytes < ibytes) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (workspace_bytes < variable_workspace_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // the copy pass reads bits, lengths and index entries of both inputs beside the ones other lanes write
+  const size_t lbytes = 2 * (size_t)p.g.nblocks;
+  if (ranges_overlap(d_src, src_bytes, d_dst, dst_capacity) || ranges_overlap(d_box, box_bytes, d_dst, dst_capacity))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ranges_overlap(d_src_lengths, lbytes, d_lengths, lbytes) ||
+      ranges_overlap(d_box_lengths, 2 * (size_t)r.nrb, d_lengths, lbytes))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (ranges_overlap(d_src_index, ibytes, d_index, ibytes) || ranges_overlap(d_box_index, box_ibytes, d_index, ibytes))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  uint64_t* offsets = (uint64_t*)d_workspace;
+  uint64_t* partials = offsets + p.g.nblocks;
+  if (type == CUZFP_TYPE_FLOAT)
+    return launch_insert_region_variable_type<float>(p, r, d_box, box_bytes, d_box_lengths, d_box_index, d_src,
+                                                     src_bytes, d_src_lengths, d_src_index, d_dst, dst_capacity / 8,
+                                                     d_lengths, d_index, d_total_bits, offsets, partials, stream);
+  return launch_insert_region_variable_type<double>(p, r, d_box, box_bytes, d_box_lengths, d_box_index, d_src,
+                                                    src_bytes, d_src_lengths, d_src_index, d_dst, dst_capacity / 8,
+                                                    d_lengths, d_index, d_total_bits, offsets, partials, stream);
+}
+
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {
   if (!d_src || !d_dst || (bytes & 15) || (((uintptr_t)d_src | (uintptr_t)d_dst) & 15))
     return CUZFP_ERROR_INVALID_ARGUMENT;

@@ -191,4 +191,27 @@ int launch_encode_region_variable_type(const Problem& p, const Region& r, const 
                                        uint64_t cap_words, uint16_t* lengths, uint64_t* dst_index, uint64_t* total,
                                        uint64_t* offsets, uint64_t* partials, hipStream_t st);
 
+// cuzfp_hip_extract_region_variable and cuzfp_hip_insert_region_variable
+// (region_variable_crop_kernels.hpp): the blocks of the block-aligned box `r`
+// moved bit for bit, out of the stream `src` into a stream of their own, or
+// from such a stream `box` into a copy of `src`.  Both write lengths, *total,
+// the new index unless dst_index is null, and `dst` below cap_words.
+//   extract: lengths, dst_index, offsets (r.nrb words) and partials
+//            (variable_tiles(r.nrb)) are the box's
+//   insert:  they are the array's (nblocks, variable_tiles(nblocks))
+// No load outside [src, src + src_bytes), src_lengths[0 .. nblocks), src_index[0
+// .. T), [box, box + box_bytes), box_lengths[0 .. r.nrb) and box_index[0 ..
+// ceil(r.nrb / 64)) whatever the indices and lengths hold.
+template <typename Scalar>
+int launch_extract_region_variable_type(unsigned dims, const Region& r, const uint64_t* src, size_t src_bytes,
+                                        const uint16_t* src_lengths, const uint64_t* src_index, uint64_t* dst,
+                                        uint64_t cap_words, uint16_t* lengths, uint64_t* dst_index, uint64_t* total,
+                                        uint64_t* offsets, uint64_t* partials, hipStream_t st);
+template <typename Scalar>
+int launch_insert_region_variable_type(const Problem& p, const Region& r, const uint64_t* box, size_t box_bytes,
+                                       const uint16_t* box_lengths, const uint64_t* box_index, const uint64_t* src,
+                                       size_t src_bytes, const uint16_t* src_lengths, const uint64_t* src_index,
+                                       uint64_t* dst, uint64_t cap_words, uint16_t* lengths, uint64_t* dst_index,
+                                       uint64_t* total, uint64_t* offsets, uint64_t* partials, hipStream_t st);
+
 }  // namespace cuzfp

@@ -513,6 +513,112 @@ int cuzfp_hip_encode_region_variable(const void* d_box, long long sx, long long 
                                      uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
                                      hipStream_t stream);
 
+/* Not reference entry points (callers test CUZFP_HIP_HAS_VARIABLE_CROP): crop a
+ * box of blocks out of a variable-rate stream into a stream of its own, and
+ * paste such a stream into a box of another -- both in the compressed domain.
+ * zfp codes every 4^d block on its own, and a block's code depends only on its
+ * values and on which of its elements lie inside the array, so both are moves
+ * of bits: nothing is decoded, nothing is coded again, the result is exact and
+ * no mode is needed.
+ *
+ * The aligned box.  Both calls take only a box that is aligned: on every used
+ * axis origin % 4 == 0, and extent % 4 == 0 or origin + extent == n.  Such a box
+ * is a union of whole blocks, and each of them has the same elements inside the
+ * box as inside the array.  Any other box is CUZFP_ERROR_INVALID_ARGUMENT;
+ * cuzfp_hip_decode_region_variable and cuzfp_hip_encode_region_variable handle
+ * partial coverage, by decoding.
+ *
+ * cuzfp_hip_extract_region_variable: the stream of the sub-array origin +
+ *   extent, as a stand-alone stream of an array of shape extent.  Box block r,
+ *   in the box's raster order (x fastest), is source block b = ((bz0 + rz) * by +
+ *   by0 + ry) * bx + bx0 + rx, copied bit for bit with its raw source length to
+ *   d_lengths[r]; the blocks lie back to back and the pad to the next 64-bit
+ *   word is zero.  Where the source is cuzfp_hip_encode_variable's (or CPU zfp
+ *   0.5.0's) stream of an array A, the result is byte for byte its stream of
+ *   A[box] at the same mode.  Unless d_index is NULL the box's offset index,
+ *   equal to cuzfp_hip_variable_index of d_lengths, goes there
+ *   (dst_index_bytes >= cuzfp_hip_variable_index_bytes of the extent: the box's
+ *   index is smaller than the source's).  Asynchronous on `stream`, no
+ *   allocation, no synchronisation (a gather of the box's lengths, a
+ *   three-launch scan, a zero fill, the copy pass).
+ * cuzfp_hip_extract_region_variable_workspace_bytes(type, ex, ey, ez): device
+ *   scratch of the call, cuzfp_hip_variable_workspace_bytes of an array of the
+ *   box's extent; 0 for invalid dimensions and integer types.
+ * cuzfp_hip_extract_region_variable_maximum_size: 8 * ceil(min(8 * src_bytes,
+ *   box_blocks * B) / 64) bytes, B the longest block of the type (what
+ *   cuzfp_hip_variable_maximum_size counts a block at, at the type's
+ *   precision).  0 for an invalid argument, a box that is not aligned included.
+ *
+ * cuzfp_hip_insert_region_variable: the stream d_src of the array (nx, ny, nz)
+ *   with the blocks of the box replaced by those of the stream d_box, out of
+ *   place like cuzfp_hip_encode_region_variable.  Block b of the result is box
+ *   block r, with d_box_lengths[r], if b lies in the box; otherwise it is its
+ *   bits of the source, unchanged, with its source length.  The blocks are
+ *   packed back to back with a zero pad.  d_box_index is
+ *   cuzfp_hip_variable_index of d_box_lengths (box_index_bytes its size),
+ *   d_src_index that of d_src_lengths (index_bytes: the source's and the
+ *   result's index have one size).  The box stream must be of the array's
+ *   scalar type and rank and hold the box's block count of blocks; the caller
+ *   states that and the call cannot check it.  The call knows no modes: a
+ *   full-precision brick may be pasted into a fixed-accuracy archive, as the
+ *   decoders need block boundaries, not the mode.  Neither input is modified.
+ *   Asynchronous on `stream`, no allocation, no synchronisation (a copy of the
+ *   source lengths, a scatter of the box lengths, a three-launch scan, a zero
+ *   fill, one copy pass over all blocks).
+ * cuzfp_hip_insert_region_variable_workspace_bytes(type, nx, ny, nz):
+ *   cuzfp_hip_variable_workspace_bytes; 0 for invalid dimensions and integer
+ *   types.
+ * cuzfp_hip_insert_region_variable_maximum_size(src_bytes, box_bytes): 8 *
+ *   ceil((8 * src_bytes + 8 * box_bytes) / 64): every block of the result is
+ *   bits of one of the two.
+ *
+ * Both calls write d_lengths (the box's block count of entries for extract,
+ * nblocks for insert), *d_total_bits, the result's ceil(total / 64) words, no
+ * byte past them and none at or past dst_capacity (if the stream does not fit,
+ * the lengths, the count and the index are still right and d_dst's contents are
+ * unspecified), and, unless d_index is NULL, the result's offset index.  d_dst
+ * == NULL with dst_capacity == 0 is the size query.  No index and no lengths
+ * array is trusted, the source's or the box's, by the decoders' rule: whatever
+ * they hold, nothing outside [d_src, d_src + src_bytes), d_src_lengths[0 ..
+ * nblocks), d_src_index[0 .. T) and, for insert, [d_box, d_box + box_bytes),
+ * d_box_lengths[0 .. box_blocks) and d_box_index[0 .. ceil(box_blocks / 64)) is
+ * read and nothing outside the outputs is written; a copied length is clamped
+ * to the type's longest block, and blocks whose entries are wrong give
+ * unspecified bits.
+ * Before any launch: CUZFP_ERROR_UNSUPPORTED_TYPE for integer and unknown
+ * types; CUZFP_ERROR_INVALID_ARGUMENT for invalid dimensions, a null pointer
+ * (d_index and, with dst_capacity 0, d_dst excepted), a misaligned one (the
+ * input streams 4 bytes, the lengths 2, the indices, d_dst, d_total_bits and
+ * the workspace 8), the box errors of cuzfp_hip_decode_region, a box that is not
+ * aligned, a short index_bytes, box_index_bytes, dst_index_bytes or workspace,
+ * and an output that overlaps an input: d_dst an input stream, d_lengths an
+ * input's lengths, d_index an input's index. */
+#define CUZFP_HIP_HAS_VARIABLE_CROP 1
+size_t cuzfp_hip_extract_region_variable_workspace_bytes(int type, unsigned ex, unsigned ey, unsigned ez);
+size_t cuzfp_hip_extract_region_variable_maximum_size(int type, unsigned nx, unsigned ny, unsigned nz,
+                                                      size_t src_bytes, unsigned ex, unsigned ey, unsigned ez,
+                                                      unsigned ox, unsigned oy, unsigned oz);
+int cuzfp_hip_extract_region_variable(const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                      const uint64_t* d_src_index, size_t index_bytes,
+                                      int type, unsigned nx, unsigned ny, unsigned nz,
+                                      unsigned ox, unsigned oy, unsigned oz,
+                                      unsigned ex, unsigned ey, unsigned ez,
+                                      uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths,
+                                      uint64_t* d_index, size_t dst_index_bytes, uint64_t* d_total_bits,
+                                      void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+size_t cuzfp_hip_insert_region_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz);
+size_t cuzfp_hip_insert_region_variable_maximum_size(size_t src_bytes, size_t box_bytes);
+int cuzfp_hip_insert_region_variable(const uint64_t* d_box, size_t box_bytes, const uint16_t* d_box_lengths,
+                                     const uint64_t* d_box_index, size_t box_index_bytes,
+                                     const uint64_t* d_src, size_t src_bytes, const uint16_t* d_src_lengths,
+                                     const uint64_t* d_src_index, size_t index_bytes,
+                                     int type, unsigned nx, unsigned ny, unsigned nz,
+                                     unsigned ox, unsigned oy, unsigned oz,
+                                     unsigned ex, unsigned ey, unsigned ez,
+                                     uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths, uint64_t* d_index,
+                                     uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
+                                     hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,
