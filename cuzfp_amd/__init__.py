@@ -23,7 +23,7 @@ __all__ = [
     "encode", "decode", "decode_region", "encode_region", "truncate", "compress_host", "decompress_host", "type_code",
     "encode_variable", "decode_variable", "accuracy_to_minexp", "variable_maximum_size",
     "variable_index", "decode_region_variable", "truncate_variable", "encode_region_variable",
-    "extract_region_variable", "insert_region_variable",
+    "extract_region_variable", "insert_region_variable", "join_variable",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -45,6 +45,12 @@ class CodecError(RuntimeError):
             msg += f" (hipError {hip_error})"
         super().__init__(msg)
         self.status = status
+
+
+class VariablePart(ctypes.Structure):
+    """cuzfp_hip_variable_part: one part of `cuzfp_hip_join_variable`."""
+    _fields_ = [("d_words", ctypes.c_void_p), ("bytes", ctypes.c_size_t), ("d_lengths", ctypes.c_void_p),
+                ("nblocks", ctypes.c_uint)]
 
 
 _lib = None
@@ -133,6 +139,13 @@ def library() -> ctypes.CDLL:
     lib.cuzfp_hip_insert_region_variable.restype = i
     lib.cuzfp_hip_insert_region_variable.argtypes = [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, i, u, u, u,
                                                      u, u, u, u, u, u, vp, sz, vp, vp, vp, vp, sz, vp]
+    lib.cuzfp_hip_join_variable_workspace_bytes.restype = sz
+    lib.cuzfp_hip_join_variable_workspace_bytes.argtypes = [i, u, u, u]
+    lib.cuzfp_hip_join_variable_maximum_size.restype = sz
+    lib.cuzfp_hip_join_variable_maximum_size.argtypes = [ctypes.POINTER(VariablePart), u]
+    lib.cuzfp_hip_join_variable.restype = i
+    lib.cuzfp_hip_join_variable.argtypes = [ctypes.POINTER(VariablePart), u, i, u, u, u, vp, sz, vp, vp, vp, vp, sz,
+                                            vp]
     lib.cuzfp_hip_compress_host.restype = i
     lib.cuzfp_hip_compress_host.argtypes = [vp, i, u, u, u, u, vp, sz, ctypes.POINTER(sz), i]
     lib.cuzfp_hip_decompress_host.restype = i
@@ -1032,7 +1045,8 @@ def insert_region_variable(box_words, box_lengths, box_index, words, lengths, in
     Assembling an array from its slabs: the stream of an all-zero array is one
     0 bit a block -- ``nblocks`` lengths of 1, ceil(nblocks / 64) zero words --
     and pasting each slab's stream into it, slab by slab, gives the stream of
-    the whole array.
+    the whole array; `join_variable` does that in one pass for slabs along the
+    slowest axis.
 
     `out` (64-bit words, overlapping neither input) is allocated at the bits of
     both inputs when None; a shorter `out` is never written past its end, but
@@ -1072,6 +1086,102 @@ def insert_region_variable(box_words, box_lengths, box_index, words, lengths, in
         index.data_ptr(), index.numel() * index.element_size(), t, nx, ny, nz, ox, oy, oz, ex, ey, ez,
         out.data_ptr() if out.numel() else None, out.numel() * 8, new_lengths.data_ptr(),
         new_index.data_ptr() if with_index else None, total.data_ptr(), ws.data_ptr(), n, _stream_handle(stream))
+    _check(where, rc)
+    with torch.cuda.stream(s):
+        nbits = int(total.item())  # the one synchronisation: the count is data dependent
+    new_words = out[: min((nbits + 63) // 64, out.numel())]
+    if with_index:
+        return new_words, new_lengths, nbits, new_index
+    return new_words, new_lengths, nbits
+
+
+JOIN_MAX_PARTS = 64  # the part table travels in the kernel arguments (kJoinMaxParts)
+
+
+def join_variable(parts, shape, dtype, out=None, stream=None, with_index=False):
+    """Concatenate the variable-rate device streams of the slabs of an array
+    into the stream of the array, in one pass and without decoding; returns
+    ``(words, lengths, nbits)`` like `encode_variable`, or ``(words, lengths,
+    nbits, index)`` with ``with_index=True``.
+
+    `parts` is a sequence of ``(words, lengths)`` or ``(words, lengths,
+    nbits)`` tuples as `encode_variable` returns them, in slab order along the
+    slowest axis of `shape`: z-slabs of a 3D array, y-slabs of a 2D one,
+    x-ranges of a 1D one.  A part's depth follows from its block count; every
+    part is a whole number of 4-deep block slabs (so every slab but the last is
+    a multiple of 4 deep), and together they are the array.  At most 64 parts.
+
+    zfp codes every block on its own and writes the blocks back to back, so
+    the parts' bits laid end to end are byte for byte what `encode_variable` --
+    and CPU zfp 0.5.0 -- writes for the whole array at the mode that wrote the
+    parts.  No mode and no index of a part is needed; parts of different modes
+    join as well, as the decoders need block boundaries, not the mode.  It is
+    the inverse of `extract_region_variable` on slabs, and replaces pasting
+    slab after slab into an all-zero archive with `insert_region_variable`.
+
+    `out` (64-bit words, overlapping no part) is allocated at the parts' bytes
+    when None; a shorter `out` is never written past its end, but then holds no
+    valid stream if nbits exceeds it.  Lengths that do not belong to their
+    streams cannot make the call read outside the parts or write outside its
+    outputs.  Asynchronous on `stream` except for one synchronisation to read
+    the count, as `encode_variable`."""
+    import torch
+    where = "join_variable"
+    t = type_code(dtype)
+    if t in (TYPE_INT32, TYPE_INT64):
+        raise CodecError(where, 2)
+    shape = tuple(int(s) for s in shape)
+    nx, ny, nz = _extents(shape)
+    if any(s <= 0 for s in shape):
+        raise ValueError(f"{where}: invalid shape {shape}")
+    parts = list(parts)
+    if not parts or len(parts) > JOIN_MAX_PARTS:
+        raise ValueError(f"{where}: takes 1 to {JOIN_MAX_PARTS} parts, not {len(parts)}")
+    nblocks = _block_count(shape)
+    slab = _block_count(shape[1:])  # the blocks of one 4-deep slab of the slowest axis
+    count = 0
+    for k, part in enumerate(parts):
+        if len(part) not in (2, 3):
+            raise ValueError(f"{where}: part {k} must be (words, lengths) or (words, lengths, nbits)")
+        words, lengths = part[0], part[1]
+        if not words.is_cuda or not lengths.is_cuda:
+            raise ValueError(f"{where}: part {k}: expects a device stream and device lengths")
+        if lengths.element_size() != 2 or not lengths.is_contiguous() or not words.is_contiguous():
+            raise ValueError(f"{where}: part {k}: lengths must be a contiguous 16-bit tensor, words contiguous")
+        if words.element_size() % 4:
+            raise ValueError(f"{where}: part {k}: words must be a tensor of 32- or 64-bit words")
+        n = lengths.numel()
+        if n == 0 or n % slab:
+            raise ValueError(f"{where}: part {k} has {n} blocks, no whole number of slabs of {slab} blocks")
+        if len(part) == 3 and int(part[2]) > 8 * words.numel() * words.element_size():
+            raise ValueError(f"{where}: part {k}: words holds fewer than its {int(part[2])} bits")
+        count += n
+    if count != nblocks:
+        raise ValueError(f"{where}: the parts have {count} blocks, the array {shape} has {nblocks}")
+    if out is not None and (not out.is_cuda or not out.is_contiguous() or out.element_size() != 8):
+        raise ValueError(f"{where}: out must be a contiguous device tensor of 64-bit words")
+    device = parts[0][0].device
+    lib = library()
+    table = (VariablePart * len(parts))()
+    for k, part in enumerate(parts):
+        table[k] = VariablePart(part[0].data_ptr(), part[0].numel() * part[0].element_size(), part[1].data_ptr(),
+                                part[1].numel())
+    n = lib.cuzfp_hip_join_variable_workspace_bytes(t, nx, ny, nz)
+    if n == 0:
+        raise CodecError(where, 1)
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.stream(s):
+        ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=device)
+        if out is None:
+            out = torch.empty(lib.cuzfp_hip_join_variable_maximum_size(table, len(parts)) // 8, dtype=torch.int64,
+                              device=device)
+        new_lengths = torch.empty(nblocks, dtype=torch.int16, device=device)
+        new_index = torch.empty((nblocks + 63) // 64 + 1, dtype=torch.int64, device=device) if with_index else None
+        total = torch.empty(1, dtype=torch.int64, device=device)
+    rc = lib.cuzfp_hip_join_variable(
+        table, len(parts), t, nx, ny, nz, out.data_ptr() if out.numel() else None, out.numel() * 8,
+        new_lengths.data_ptr(), new_index.data_ptr() if with_index else None, total.data_ptr(), ws.data_ptr(), n,
+        ctypes.c_void_p(s.cuda_stream))
     _check(where, rc)
     with torch.cuda.stream(s):
         nbits = int(total.item())  # the one synchronisation: the count is data dependent

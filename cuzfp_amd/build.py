@@ -33,13 +33,13 @@ KERNEL_UNITS = ["inst_f32", "inst_f64", "inst_i32", "inst_i64",
                 "variable_f32", "variable_f64", "region_variable_f32", "region_variable_f64", "truncate_variable",
                 "region_variable_coarse_f32", "region_variable_coarse_f64",
                 "region_variable_update_f32", "region_variable_update_f64",
-                "region_variable_crop_f32", "region_variable_crop_f64",
+                "region_variable_crop_f32", "region_variable_crop_f64", "join_variable",
                 "capi"]
 HEADERS = ["zfp_block.hpp", "kernels.hpp", "launch.hpp", "wave_index.hpp", "region.hpp", "region_kernels.hpp",
            "region_update_kernels.hpp", "rerate.hpp", "variable_kernels.hpp", "variable_index.hpp",
            "region_variable_kernels.hpp", "rerate_variable.hpp", "source_window.hpp", "variable_coarse.hpp",
            "region_variable_coarse_kernels.hpp", "region_variable_update_kernels.hpp",
-           "region_variable_crop_kernels.hpp"]
+           "region_variable_crop_kernels.hpp", "join_variable.hpp"]
 
 
 def _newer(target: str, deps: list[str]) -> bool:

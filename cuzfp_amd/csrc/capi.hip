@@ -9,6 +9,7 @@
 #include <chrono>
 #include <vector>
 
+#include "join_variable.hpp"
 #include "launch.hpp"
 #include "rerate_variable.hpp"
 #include "variable_index.hpp"
@@ -1398,6 +1399,84 @@ int cuzfp_hip_insert_region_variable(const uint64_t* d_box, size_t box_bytes, co
   return launch_insert_region_variable_type<double>(p, r, d_box, box_bytes, d_box_lengths, d_box_index, d_src,
                                                     src_bytes, d_src_lengths, d_src_index, d_dst, dst_capacity / 8,
                                                     d_lengths, d_index, d_total_bits, offsets, partials, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Join of the variable-rate streams of slabs (join_variable.hip)
+
+size_t cuzfp_hip_join_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz) {
+  return cuzfp_hip_variable_workspace_bytes(type, nx, ny, nz);
+}
+
+// the bytes of all parts; false where the table is no table or the bits would wrap
+static bool join_parts_bytes(const cuzfp_hip_variable_part* parts, unsigned nparts, size_t* sum) {
+  if (!parts || !nparts || nparts > kJoinMaxParts) return false;
+  size_t s = 0;
+  for (unsigned k = 0; k < nparts; k++) {
+    if (parts[k].bytes > ((size_t)1 << 52)) return false;  // 64 parts of 2^52 bytes: 8 * sum must not wrap
+    s += parts[k].bytes;
+  }
+  *sum = s;
+  return true;
+}
+
+size_t cuzfp_hip_join_variable_maximum_size(const cuzfp_hip_variable_part* parts, unsigned nparts) {
+  size_t s;
+  if (!join_parts_bytes(parts, nparts, &s)) return 0;
+  return 8 * ((8 * s + 63) / 64);
+}
+
+int cuzfp_hip_join_variable(const cuzfp_hip_variable_part* parts, unsigned nparts, int type,
+                            unsigned nx, unsigned ny, unsigned nz, uint64_t* d_dst, size_t dst_capacity,
+                            uint16_t* d_lengths, uint64_t* d_index, uint64_t* d_total_bits, void* d_workspace,
+                            size_t workspace_bytes, hipStream_t stream) {
+  Problem p;
+  int rc = make_variable_problem(type, nx, ny, nz, 0, 0, 0, &p);
+  if (rc) return rc;
+  size_t sum;
+  if (!join_parts_bytes(parts, nparts, &sum)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_lengths || !d_total_bits || !d_workspace) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (!d_dst && dst_capacity) return CUZFP_ERROR_INVALID_ARGUMENT;
+  if (((uintptr_t)d_lengths & 1) ||
+      (((uintptr_t)d_dst | (uintptr_t)d_index | (uintptr_t)d_total_bits | (uintptr_t)d_workspace) & 7))
+    return CUZFP_ERROR_INVALID_ARGUMENT;
+  // a part is a whole number of 4-deep slabs of the slowest axis, and the parts are the array
+  const uint64_t slab = p.dims == 3 ? (uint64_t)p.g.bx * p.g.by : p.dims == 2 ? p.g.bx : 1;
+  JoinParts tab = {};
+  uint64_t first = 0;
+  for (unsigned k = 0; k < nparts; k++) {
+    const cuzfp_hip_variable_part& q = parts[k];
+    if (!q.d_words || !q.d_lengths || ((uintptr_t)q.d_words & 3) || ((uintptr_t)q.d_lengths & 1))
+      return CUZFP_ERROR_INVALID_ARGUMENT;
+    if (!q.nblocks || q.nblocks % slab) return CUZFP_ERROR_INVALID_ARGUMENT;
+    tab.words[k] = (const uint32_t*)q.d_words;
+    tab.dwords[k] = q.bytes / 4;
+    tab.lengths[k] = q.d_lengths;
+    tab.first[k] = (uint32_t)first;
+    tab.longest = std::max(tab.longest, q.nblocks);
+    first += q.nblocks;
+    if (first > p.g.nblocks) return CUZFP_ERROR_INVALID_ARGUMENT;
+  }
+  if (first != p.g.nblocks) return CUZFP_ERROR_INVALID_ARGUMENT;
+  tab.first[nparts] = p.g.nblocks;
+  tab.nparts = nparts;
+  if (workspace_bytes < variable_workspace_of(p.g)) return CUZFP_ERROR_INVALID_ARGUMENT;
+  // every kernel reads the parts beside what other lanes write
+  const size_t lbytes = 2 * (size_t)p.g.nblocks, ibytes = variable_index_bytes_of(p.g);
+  for (unsigned k = 0; k < nparts; k++) {
+    const cuzfp_hip_variable_part& q = parts[k];
+    const void* in[2] = {q.d_words, q.d_lengths};
+    const size_t nin[2] = {q.bytes, 2 * (size_t)q.nblocks};
+    for (int j = 0; j < 2; j++)
+      if (ranges_overlap(in[j], nin[j], d_dst, dst_capacity) || ranges_overlap(in[j], nin[j], d_lengths, lbytes) ||
+          ranges_overlap(in[j], nin[j], d_index, ibytes) || ranges_overlap(in[j], nin[j], d_total_bits, 8) ||
+          ranges_overlap(in[j], nin[j], d_workspace, variable_workspace_of(p.g)))
+        return CUZFP_ERROR_INVALID_ARGUMENT;
+  }
+  uint64_t* offsets = (uint64_t*)d_workspace;
+  uint64_t* partials = offsets + p.g.nblocks;
+  return launch_join_variable(tab, p.g.nblocks, (8 * (uint64_t)sum + 63) / 64, d_dst, dst_capacity / 8, d_lengths,
+                              d_index, d_total_bits, offsets, partials, stream);
 }
 
 int cuzfp_hip_copy(const void* d_src, void* d_dst, size_t bytes, hipStream_t stream) {

@@ -214,4 +214,17 @@ int launch_insert_region_variable_type(const Problem& p, const Region& r, const 
                                        uint64_t* dst, uint64_t cap_words, uint16_t* lengths, uint64_t* dst_index,
                                        uint64_t* total, uint64_t* offsets, uint64_t* partials, hipStream_t st);
 
+// cuzfp_hip_join_variable (join_variable.hip): the streams of the parts of
+// `tab` (join_variable.hpp; consecutive runs of the array's blocks in raster
+// order) concatenated: lengths, *total, the index unless dst_index is null, and
+// `dst` below cap_words (0: none).  bound_words: the words of all parts
+// together, which sizes the copy's grid.  offsets holds nblocks words, partials
+// variable_tiles(nblocks).  One instantiation for every type and rank.  No load
+// outside the parts' [words, words + 4 dwords) and lengths whatever the lengths
+// hold.
+struct JoinParts;
+int launch_join_variable(const JoinParts& tab, uint32_t nblocks, uint64_t bound_words, uint64_t* dst,
+                         uint64_t cap_words, uint16_t* lengths, uint64_t* dst_index, uint64_t* total,
+                         uint64_t* offsets, uint64_t* partials, hipStream_t st);
+
 }  // namespace cuzfp

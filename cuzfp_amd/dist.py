@@ -73,6 +73,54 @@ def allgather_stream(local_words, group=None):
     return out
 
 
+ALLGATHER_VARIABLE_MAX_WORLD = 64  # join_variable's part table (cuzfp_amd.JOIN_MAX_PARTS)
+
+
+def allgather_variable(words, lengths, nbits, shape, dtype, group=None, with_index=False):
+    """The variable-rate counterpart of `allgather_stream`.  Every rank holds
+    ``(words, lengths, nbits)`` of `encode_variable` of its `slab_extent` slab
+    of the array of `shape`; every rank gets ``(words, lengths, nbits)`` of the
+    whole array (``(..., index)`` with ``with_index=True``), byte for byte
+    `encode_variable` of it.
+
+    A slab's stream ends at an arbitrary bit, so the segments cannot be laid
+    side by side as the fixed-rate ones are.  The ranks exchange their (word
+    count, block count), pad words and lengths to the largest rank's, gather
+    both with one `allgather_stream` each -- on the device under RCCL, through
+    the host under gloo -- and join the K views with `cuzfp_amd.join_variable`
+    on the device of `words`.  A rank whose slab is empty (more ranks than 4-deep
+    slabs) passes empty tensors and 0 and contributes no part.  At most 64
+    ranks."""
+    import torch
+    import torch.distributed as dist
+
+    from . import join_variable
+    world = dist.get_world_size(group)
+    if world > ALLGATHER_VARIABLE_MAX_WORLD:
+        raise ValueError(f"allgather_variable: {world} ranks, join_variable takes at most "
+                         f"{ALLGATHER_VARIABLE_MAX_WORLD} parts")
+    if not words.is_cuda or not lengths.is_cuda:
+        raise ValueError("allgather_variable: expects a device stream and device lengths")
+    if words.element_size() != 8 or lengths.element_size() != 2:
+        raise ValueError("allgather_variable: words must be 64-bit and lengths 16-bit, as encode_variable returns them")
+    nw, nb = (int(nbits) + 63) // 64, lengths.numel()
+    if nw > words.numel():
+        raise ValueError(f"allgather_variable: words holds {words.numel()} words, {nbits} bits need {nw}")
+    device = words.device
+    via = torch.device("cpu") if dist.get_backend(group) == "gloo" else device
+    counts = allgather_stream(torch.tensor([nw, nb], dtype=torch.int64).to(via), group).cpu().view(world, 2)
+    maxw, maxb = int(counts[:, 0].max()), int(counts[:, 1].max())
+    wpad = torch.zeros(maxw, dtype=torch.int64, device=via)
+    lpad = torch.zeros(maxb, dtype=torch.int16, device=via)
+    wpad[:nw] = words.reshape(-1)[:nw].view(torch.int64)
+    lpad[:nb] = lengths.reshape(-1).view(torch.int16)
+    gw = allgather_stream(wpad, group).to(device)
+    gl = allgather_stream(lpad.view(torch.uint8), group).view(torch.int16).to(device)  # neither backend moves int16
+    parts = [(gw[r * maxw: r * maxw + int(counts[r, 0])], gl[r * maxb: r * maxb + int(counts[r, 1])])
+             for r in range(world) if int(counts[r, 1])]
+    return join_variable(parts, shape, dtype, with_index=with_index)
+
+
 def stream_offset_words(shape, world: int, rank: int, maxbits: int) -> int:
     """Word offset of `rank`'s segment in the global stream (uniform sharding)."""
     return rank * segment_words(shape, world, maxbits)
@@ -124,4 +172,4 @@ def sharded_summary(shard: "StrongShard", itemsize: int, step_s: float, enc_s: l
 
 
 __all__ = ["StrongShard", "sharded_summary", "slab_extent", "blocks_per_slab", "uniform_shard_ok", "segment_words",
-           "local_shape", "allgather_stream", "stream_offset_words"]
+           "local_shape", "allgather_stream", "stream_offset_words", "allgather_variable"]

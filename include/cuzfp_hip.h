@@ -619,6 +619,69 @@ int cuzfp_hip_insert_region_variable(const uint64_t* d_box, size_t box_bytes, co
                                      uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
                                      hipStream_t stream);
 
+/* Not a reference entry point (callers test CUZFP_HIP_HAS_VARIABLE_JOIN): the
+ * variable-rate streams of K slabs of an array concatenated into the stream of
+ * the array, in one pass and in the compressed domain.  zfp codes every block
+ * on its own and writes the blocks back to back in raster order, so the stream
+ * of an array is the streams of its z-slabs (3D; y-slabs in 2D, x-ranges in 1D)
+ * one after the other, bit for bit -- where every slab but the last is a
+ * multiple of 4 deep.  A slab's stream ends at an arbitrary bit, so the join is
+ * a funnel shift, not a copy.  It is the inverse of
+ * cuzfp_hip_extract_region_variable on slabs.
+ *
+ * parts: a host array of nparts entries, read before the call returns.  Part k
+ *   is the stream [d_words, d_words + bytes) (device memory, as
+ *   cuzfp_hip_encode_variable wrote it) of nblocks blocks with its raw lengths
+ *   d_lengths[0 .. nblocks); the parts hold the result's blocks [B_k, B_{k+1})
+ *   in order, B_k the sum of the nblocks before k.  nblocks is a positive
+ *   multiple of the blocks in one 4-deep slab of the slowest axis (bx * by in
+ *   3D, bx in 2D, 1 in 1D) and the nblocks sum to the array's block count.  The
+ *   call takes at most 64 parts: the table travels in the kernel arguments, so
+ *   there is no host-to-device copy, no allocation and no synchronisation, and
+ *   the call can be captured into a graph.  No index of a part is needed.
+ * The result: d_lengths = the parts' lengths concatenated (nblocks entries);
+ *   *d_total_bits = their sum; the stream's bits [O_k, O_{k+1}) = part k's bits
+ *   [0, O_{k+1} - O_k), O_k the sum of the lengths before block B_k; a zero pad
+ *   to the next 64-bit word; unless d_index is NULL, the offset index
+ *   (cuzfp_hip_variable_index_bytes of the array), equal to
+ *   cuzfp_hip_variable_index of d_lengths.  ceil(total / 64) words are written,
+ *   each once, no byte past them and none at or past dst_capacity (if the stream
+ *   does not fit, the lengths, the count and the index are still right and
+ *   d_dst's contents are unspecified).  d_dst == NULL with dst_capacity == 0 is
+ *   the size query.  No part is modified.  Asynchronous on `stream` (a gather of
+ *   the lengths, a three-launch scan, the index, one copy pass).
+ * cuzfp_hip_join_variable_workspace_bytes: cuzfp_hip_variable_workspace_bytes;
+ *   0 for invalid dimensions and integer types.
+ * cuzfp_hip_join_variable_maximum_size: 8 * ceil(8 * sum(bytes) / 64): every
+ *   bit of the result is a bit of a part.  0 for a NULL table, nparts of 0 or
+ *   above 64, or byte counts whose bits would wrap.
+ * The lengths are not trusted: whatever they hold, nothing outside the parts'
+ *   [d_words, d_words + bytes) and d_lengths[0 .. nblocks) is read, nothing
+ *   outside the outputs is written, d_lengths, the total and the index are the
+ *   raw concatenation and its sums, and the stream's words are unspecified where
+ *   a part's lengths do not belong to it.
+ * Before any launch: CUZFP_ERROR_UNSUPPORTED_TYPE for integer and unknown
+ *   types; CUZFP_ERROR_INVALID_ARGUMENT for invalid dimensions, a NULL table,
+ *   nparts of 0 or above 64, a part whose nblocks is 0 or no whole number of
+ *   slabs, nblocks that do not sum to the array's block count, a null pointer
+ *   (d_index and, with dst_capacity 0, d_dst excepted), a misaligned one (part
+ *   streams 4 bytes, lengths 2, d_dst, d_index, d_total_bits and the workspace
+ *   8), a short workspace, and an output (d_dst, d_lengths, d_index,
+ *   d_total_bits, the workspace) that overlaps a part's stream or lengths. */
+#define CUZFP_HIP_HAS_VARIABLE_JOIN 1
+typedef struct {
+  const uint64_t* d_words;   /* the part's stream, 4-byte aligned */
+  size_t bytes;              /* ... and its size */
+  const uint16_t* d_lengths; /* the raw length of each of its blocks */
+  unsigned nblocks;          /* how many */
+} cuzfp_hip_variable_part;
+size_t cuzfp_hip_join_variable_workspace_bytes(int type, unsigned nx, unsigned ny, unsigned nz);
+size_t cuzfp_hip_join_variable_maximum_size(const cuzfp_hip_variable_part* parts, unsigned nparts);
+int cuzfp_hip_join_variable(const cuzfp_hip_variable_part* parts, unsigned nparts,
+                            int type, unsigned nx, unsigned ny, unsigned nz,
+                            uint64_t* d_dst, size_t dst_capacity, uint16_t* d_lengths, uint64_t* d_index,
+                            uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* Host-memory end to end: the array and the stream live in
  * host memory; the library moves them in z-slab (3D) / y-slab (2D) / x-range
  * (1D) chunks on three HIP streams -- input copies, kernels, output copies,
